@@ -28,6 +28,19 @@ Launch: python bench.py [--gpus N --steps K --warmup W]; N > 1 through
 torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env).
 Rank 0 prints ONE JSON line.  Data: synthetic N(0, 3) genomes (the
 "evolved" distribution of SURVEY 8d), seeded per rank layout.
+
+A plain run does what the headline figure needs: set-up, W warm-up steps, K
+timed steps, the result line (value, ms_per_step, the workload's counters).
+  --full             adds what takes measurements of its own: the roofline
+                     block (HIP events around every evaluation launch, the
+                     committed PMC summaries) and the CPU baseline (the numpy
+                     loop on a process pool and one core, the C port;
+                     --no-cpu-baseline leaves that leg out);
+  --dump-outputs DIR writes what the last timed step computed (fitness,
+                     logbook row, the evaluation's results, hall-of-fame
+                     fitness, seeded row samples of the population and the
+                     hall of fame) as DIR/<name>.npy: equal arguments give
+                     equal inputs, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -74,7 +87,12 @@ def parse():
     p.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
     p.add_argument("--cpu-threads", type=int, default=16,
                    help="CPU baseline pool: this box's CPU share per GPU (the pool's rule on a one-GPU box)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    p.add_argument("--full", action="store_true",
+                   help="also report what the headline figure does not need: the roofline block (HIP events around "
+                        "every evaluation launch, the committed PMC summaries) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     a = p.parse_args()
     wide = a.config == "wide"
     # presets: a wide generation takes ~30 s at 65 536 genomes, so fewer steps
@@ -83,6 +101,8 @@ def parse():
     a.warmup = a.warmup if a.warmup is not None else (0 if wide else 2)
     a.shape = a.shape or ("6,512,512,3" if wide else "6,64,3")
     a.dtype = a.dtype or ("float32" if wide else "float64")
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -92,7 +112,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     cpu_pool = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the CPU baseline's worker processes are forked now, before anything touches the GPU
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import numpy_loop
@@ -187,10 +207,11 @@ def main():
     events = []
     probe_local = [0, 0, 0]  # diagnostic builds (PG_DECIDE_PROBE, PG_START_PROBE): counters[13..15]
     for s in range(args.steps):
-        # a fresh pair per step, read after the timed region: no per-step sync
-        ga.eval_events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        events.append(ga.eval_events)
-        ga.step()  # evaluate + all-gather + hall of fame + select + vary (one generation)
+        if args.full:
+            # a fresh pair per step, read after the timed region: no per-step sync
+            ga.eval_events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            events.append(ga.eval_events)
+        rec = ga.step()  # evaluate + all-gather + hall of fame + select + vary (one generation)
         counters.append(ga.last.counters.clone())
     ga.eval_events = None
     torch.cuda.synchronize(dev)
@@ -199,6 +220,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ga, rec, args.seed)
     for c in counters:
         c = c.cpu()
         steps_local += int(c[0])
@@ -238,7 +261,7 @@ def main():
     if rank == 0 and args.config == "wide":
         out = wide_report(args, world, shape, G, dtype, P, n_local, H, tournsize, elapsed, steps_all, fwd_all,
                           passes_all, kernel_ms_mean, skip_all)
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline: rank 0 at N=1 only
+        if cpu_pool is not None:  # the CPU baseline (--full): rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args, shape, ga, chunk=8, max_rows=256, pool=cpu_pool)
             cpu_pool.close()
         print(json.dumps(out), flush=True)
@@ -254,12 +277,6 @@ def main():
         episode_all = stepped_all + skip_all + hidden_all
         env_steps_per_s = stepped_all / elapsed
         ms_per_step = elapsed * 1000.0 / args.steps
-        # roofline of the dominant kernel (k_service), per launch on rank 0's timing
-        flops_per_forward = 2.0 * G
-        fwd_per_launch = fwd_all / world / args.steps
-        steps_per_launch = stepped_all / world / args.steps
-        achieved_tflops = fwd_per_launch * flops_per_forward / (kernel_ms_mean / 1e3) / 1e12
-        streaming_bytes = steps_per_launch * (2 * 4 * G + 128)   # SURVEY 8d accounting, GB-equivalent
         sched = ("self-play games vs the hall of fame" if args.schedule == "selfplay" else
                  "evaluate()'s schedule (main.py:33-53: HardcodedAi, the 1-player CPU, ScoreHardcodedAi, 3 hall-of-fame games)")
         mode = (f"fixed horizon: every game slot {args.horizon} frames, auto-reset (SURVEY 8d)" if args.horizon
@@ -299,16 +316,63 @@ def main():
                        "failures_decided_by_f64_certificate": cert_all[1] / max(cert_all[0], 1.0),
                        "numpy_order_f64_forwards_per_forward": slow_all / max(fwd_all, 1.0),
                        **({"probe_counters_13_15": probe_local} if probe_local[2] else {})},
-            "roofline": _selfplay_roofline(args, G, dtype, achieved_tflops, kernel_ms_mean, flops_per_forward,
-                                           fwd_per_launch, steps_per_launch, streaming_bytes, n_local, H),
         }
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline: rank 0 at N=1 only
+        if args.full:
+            # roofline of the dominant kernel (k_service), per launch on rank 0's timing
+            flops_per_forward = 2.0 * G
+            fwd_per_launch = fwd_all / world / args.steps
+            steps_per_launch = stepped_all / world / args.steps
+            achieved_tflops = fwd_per_launch * flops_per_forward / (kernel_ms_mean / 1e3) / 1e12
+            streaming_bytes = steps_per_launch * (2 * 4 * G + 128)   # SURVEY 8d accounting, GB-equivalent
+            out["roofline"] = _selfplay_roofline(args, G, dtype, achieved_tflops, kernel_ms_mean, flops_per_forward,
+                                                 fwd_per_launch, steps_per_launch, streaming_bytes, n_local, H)
+        if cpu_pool is not None:  # the CPU baseline (--full): rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(args, shape, ga, pool=cpu_pool)
             cpu_pool.close()
         print(json.dumps(out), flush=True)
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 16 << 20  # per sampled genome array; every dump stays far below 64 MB in all
+
+
+def dump_outputs(out_dir, ga, rec, seed):
+    """--dump-outputs: what a caller of DeviceGA.step() holds after the last
+    timed step, one DIR/<name>.npy each (float64, genomes in their storage
+    dtype).  The inputs are seeded, so two builds run with the same arguments
+    can be compared array for array.  The [P, G] population and [H, G] hall of
+    fame are sampled: the same seeded rows every run, at most 16 MiB each."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize(ga.device)
+
+    def save(name, t):
+        a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        if a.dtype != np.float32:
+            a = a.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+    def sample(name, rows, salt):
+        n = rows.shape[0]
+        k = min(n, max(1, DUMP_BUDGET_BYTES // (ga.G * rows.element_size())))
+        idx = np.sort(np.random.default_rng([seed, salt]).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+        save(name + "_rows", idx)
+        save(name, rows[torch.as_tensor(idx, device=rows.device)])
+
+    # the logbook row step() returned (main.py:158-162's statistics)
+    save("logbook", [rec["gen"], rec["nevals"]] + [rec[f] for f in ("avg", "std", "min", "max")])
+    save("fitness", ga.fitness)                      # [P]: every individual's fitness after the step
+    save("hof_fitness", ga.hof_member_fitness)       # [hof_n], best first
+    # the step's evaluation (EvalResult of this rank's rows, in evaluation order)
+    n_played = int(ga.last_count[0]) if ga.last_count is not None else ga.last.fitness.shape[0]
+    save("eval_rows", ga.last_rows[:n_played] if ga.last_rows is not None else np.arange(ga.lo, ga.hi))
+    save("eval_fitness", ga.last.fitness[:n_played])
+    save("eval_frames", ga.last.frames[:n_played])
+    save("eval_counters", ga.last.counters)
+    sample("population", ga.shard_rows(), 1)          # [P, G] offspring of the step (this rank's shard)
+    if ga.hof_n:
+        sample("hall_of_fame", ga.hall_of_fame, 2)    # [hof_n, G], best first
 
 
 def _selfplay_roofline(args, G, dtype, achieved_tflops, kernel_ms_mean, flops_per_forward, fwd_per_launch,
@@ -371,17 +435,7 @@ def wide_report(args, world, shape, G, dtype, P, n_local, H, tournsize, elapsed,
     per launch over the launch time against the 8 TB/s HBM peak."""
     wt = 4 if dtype == torch.float32 else 8
     ms_per_step = elapsed * 1000.0 / args.steps
-    passes_per_launch = passes_all / world / args.steps
-    steps_per_launch = steps_all / world / args.steps
-    bytes_per_launch = passes_per_launch * G * wt
-    achieved = bytes_per_launch / (kernel_ms_mean / 1e3) / 1e9
-    survey_bytes = steps_per_launch * (2 * 4 * G + 128)  # SURVEY 8d: both networks streamed per env-step
-    pmc, pmc_src = _pmc("pmc_traffic_wide.json")
-    traffic = pmc.get("traffic_bytes_fetch_x2") if pmc else None
-    stale = _pmc_stale(pmc)
-    if stale:
-        traffic = None
-    return {
+    out = {
         "metric": "env-steps/sec (GA evaluation loop, self-play, wide MLP) + generations/sec at pop=65536",
         "value": steps_all / elapsed,  # env-steps stepped frame by frame (periodic rallies jumped: a side field)
         "unit": "env-steps/s",
@@ -409,6 +463,20 @@ def wide_report(args, world, shape, G, dtype, P, n_local, H, tournsize, elapsed,
                    "periodic_rally_frames_advanced_per_generation": skip_all / args.steps,
                    "network_passes_per_generation": passes_all / args.steps,
                    "forwards_per_network_pass": fwd_all / max(passes_all, 1.0)},
+    }
+    if not args.full:
+        return out
+    passes_per_launch = passes_all / world / args.steps
+    steps_per_launch = steps_all / world / args.steps
+    bytes_per_launch = passes_per_launch * G * wt
+    achieved = bytes_per_launch / (kernel_ms_mean / 1e3) / 1e9
+    survey_bytes = steps_per_launch * (2 * 4 * G + 128)  # both networks streamed per env-step
+    pmc, pmc_src = _pmc("pmc_traffic_wide.json")
+    traffic = pmc.get("traffic_bytes_fetch_x2") if pmc else None
+    stale = _pmc_stale(pmc)
+    if stale:
+        traffic = None
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": stale,
                      "traffic_over_algorithmic": (traffic / bytes_per_launch) if traffic else None,
@@ -428,7 +496,8 @@ def wide_report(args, world, shape, G, dtype, P, n_local, H, tournsize, elapsed,
                              "survey_algorithmic counts both networks' genes per env-step (SURVEY 8d), which the "
                              "lockstep genome pass amortises over the genome's games",
                      **_measured_ceiling(achieved)},
-    }
+    })
+    return out
 
 
 def _measured_ceiling(achieved_gbps):
