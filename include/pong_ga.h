@@ -27,6 +27,8 @@
  * pg_decide                      get_actions' model.run argmax (main.py:143-150) as the
  *                                hot kernel decides it (test / fixture entry point)
  * pg_wide_decide                 the same, as k_wide decides it (config 5 networks)
+ * pg_relu_decide                 the same, as k_relu decides it (ReLU networks: numpy_nn.py:6-9,
+ *                                the "alternative activation function" of numpy_nn.py:26)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
  *                                (the build's SoA Pong; the emulator is absent)
  * pg_ga_select_tournament        tools.selTournament (ga.py:94; DEAP)
@@ -67,7 +69,7 @@
 extern "C" {
 #endif
 
-#define PG_ABI_VERSION 12
+#define PG_ABI_VERSION 13
 #define PG_MAX_NODES 9 /* len(NETWORK_SHAPE) <= 9 */
 
 typedef enum pg_status {
@@ -78,6 +80,13 @@ typedef enum pg_status {
 } pg_status;
 
 typedef enum pg_dtype { PG_F32 = 0, PG_F64 = 1 } pg_dtype;
+
+/* activation_function (numpy_nn.py:26), applied to every layer, the output
+ * layer included (NeuralNetwork.run numpy_nn.py:126-131). */
+typedef enum pg_activation {
+  PG_ACT_SIGMOID = 0, /* sigmoid numpy_nn.py:22-23: 1 / (1 + np.e ** -x) */
+  PG_ACT_RELU = 1     /* ReLU numpy_nn.py:6-9: np.maximum(0.0, x) */
+} pg_activation;
 
 /* Left-paddle opponent of one game (the genome always plays the right paddle,
  * main.py:58 right_model). */
@@ -98,7 +107,7 @@ typedef enum pg_precision {
 } pg_precision;
 
 typedef enum pg_kernel {
-  PG_KERNEL_AUTO = 0,      /* SPLIT when the shape and precision allow, else GENERAL */
+  PG_KERNEL_AUTO = 0,      /* SPLIT when the shape and precision allow, else GENERAL (ReLU nets: RELU, else GENERAL) */
   PG_KERNEL_GENERAL = 1,   /* one wave per game, f64, any NETWORK_SHAPE */
   PG_KERNEL_RESIDENT = 2,  /* retired (round 4): PG_ERR_UNSUPPORTED */
   PG_KERNEL_SPLIT = 3      /* [6, H<=256, 2..4]: half a lane group per paddle's network; f32 forwards with
@@ -108,7 +117,12 @@ typedef enum pg_kernel {
                               games (up to 6; more: balanced chunks of <= 6, one workgroup pass each)
                               in lockstep and streams W2 from HBM each frame
                               (numpy_nn's f64 order; AUTO picks it for H1 or H2 >= 64) */
-  PG_KERNEL_STAGED = 5     /* retired (round 4): PG_ERR_UNSUPPORTED */
+  PG_KERNEL_STAGED = 5,    /* retired (round 4): PG_ERR_UNSUPPORTED */
+  PG_KERNEL_RELU = 6       /* ABI 13, PG_ACT_RELU only: [6, H<=256, 2..4] with bias, certified precision: half
+                              a lane group per paddle's network, f32 weights resident for the game, the
+                              f64 argmax of max(0, z) proven from a static f32 error bound, else recomputed
+                              in f64 by the half-group in numpy's order.  AUTO picks it for
+                              exactly that scope; every other ReLU configuration runs on GENERAL */
 } pg_kernel;
 
 /* pg_eval_args.prep: the SPLIT kernel's lane records (one per network of the
@@ -129,6 +143,10 @@ typedef struct pg_net {
   int32_t nodes[PG_MAX_NODES];   /* nodes[0] = 6 for the game loop */
   int32_t bias;                  /* 1 = BIAS, weight rows are (in + 1) wide */
   int32_t dtype;                 /* pg_dtype of genomes and opponents */
+  int32_t activation;            /* ABI 13: pg_activation; 0 (a zero-initialised net) = the sigmoid.  ReLU
+                                    networks run on PG_KERNEL_RELU / PG_KERNEL_GENERAL and pg_forward (always
+                                    f64) only: pg_decide, pg_wide_decide, PG_KERNEL_SPLIT, PG_KERNEL_WIDE,
+                                    horizon > 0 and hard_log return PG_ERR_UNSUPPORTED for them */
 } pg_net;
 
 typedef struct pg_eval_args {
@@ -159,7 +177,7 @@ typedef struct pg_eval_args {
   double *total_frames;          /* [n_genomes, n_games] main.py:73 accumulator */
   int32_t *status;               /* [n_genomes] 1 = ZeroDivisionError in calculate_reward */
   uint64_t *counters;            /* optional [16], zeroed by the call: [0] env steps stepped one frame at a time, [1] NN
-                                    forwards, [2] numpy-order f64 forwards, [3] games; split kernel: [4]
+                                    forwards, [2] numpy-order f64 forwards, [3] games; split and ReLU kernels: [4]
                                     f32 certificate failures, [5] failures decided by the certified f64
                                     rules (plateau, gap), [6] failures decided in-wave by the f32 plateau
                                     rule; wide kernel: [7] network weight passes; split and wide
@@ -271,6 +289,25 @@ typedef struct pg_wide_decide_args {
   void *workspace;               /* device, pg_wide_decide_workspace_bytes */
   size_t workspace_bytes;
 } pg_wide_decide_args;
+
+/* The ReLU kernel's decision for given inputs (ABI 13): pass i is ReLU network
+ * row genome_index[i] (i if NULL) on the doubled-centroid features k[i][0..5].
+ * It runs the very decision code k_relu runs in a game: the f32 pass, the
+ * certificate under the network's static bound, and for the undecided the f64
+ * forward in numpy's order.  [6, H <= 256, 2..4] networks with bias. */
+typedef struct pg_relu_decide_args {
+  pg_net net;                    /* activation = PG_ACT_RELU */
+  int32_t n;
+  const void *genomes;           /* [*, genome_stride] (net.dtype) */
+  int64_t genome_stride;
+  const int32_t *genome_index;   /* [n] or NULL */
+  const int32_t *k;              /* [n, 6] doubled centroids, each in [0, 320] */
+  int32_t *index;                /* out [n] np.argmax of the output activations (first maximum) */
+  int32_t *stage;                /* optional out [n]: 0 decided by the f32 certificate, 1 recomputed in f64 */
+  float *z32;                    /* optional out [n, nodes[2]]: the f32 output pre-activations */
+  float *bound;                  /* optional out [n]: the certificate's bound on |z32 - z64|; inf = the
+                                    network is always decided in f64 */
+} pg_relu_decide_args;
 
 /* Struct-of-arrays game state: int32 [PG_STATE_FIELDS, n], field f of game i
  * at state[f * n + i]; 64 bytes per game. */
@@ -483,6 +520,7 @@ int32_t pg_forward(const pg_forward_args *args, void *stream);
 int32_t pg_decide(const pg_decide_args *args, void *stream);
 size_t pg_wide_decide_workspace_bytes(const pg_wide_decide_args *args);
 int32_t pg_wide_decide(const pg_wide_decide_args *args, void *stream);
+int32_t pg_relu_decide(const pg_relu_decide_args *args, void *stream);
 int32_t pg_physics_reset(int32_t *state, int32_t n, const uint64_t *seeds,
                          const int32_t *one_player, void *stream);
 /* actions [n]: bit0 right up, bit1 right down, bit2 left up, bit3 left down */

@@ -64,6 +64,11 @@ PHYSICS_SEED = 0
 # "certified": f32 hidden math whose f64 argmax is proven per decision (f64
 # re-decision otherwise); "f64": numpy_nn's f64 arithmetic for every pass.
 PRECISION = "certified"
+# The networks' activation_function (the reference selects it with one line,
+# numpy_nn.py:26): "sigmoid" (numpy_nn.py:22-23) or "relu" (numpy_nn.py:6-9, the
+# "alternative activation function"), applied to every layer.  The drop-in
+# numpy_nn.activation_function starts from it.
+ACTIVATION = "sigmoid"
 # Storage type of genomes on the device; float64 keeps Python floats exact.
 GENOME_DTYPE = "float64"
 # "cuda" = the process's current HIP device (one process per GPU).

@@ -59,6 +59,7 @@ struct EvalParams {
   const int32_t *wide_probe_k;
   int32_t *wide_probe_index;  // out [n_genomes] np.argmax
   double *wide_probe_act;     // optional out [n_genomes, nodes[3]]
+  int activation;             // pg_net.activation (k_general, k_relu)
 };
 
 // Genome blocks / games this launch plays (pg_eval_args.n_active).  Made
@@ -150,6 +151,11 @@ int32_t launch_decide(const DecideParams &p, int L, int O, bool f64, size_t lds,
 bool wide_shape_ok(const pg_net &n, int n_games);
 size_t wide_workspace_bytes(const pg_eval_args *a);
 int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s);
+
+// [6, H <= 256, 2..4] ReLU networks with bias on k_relu (pg_relu.hip): the
+// shapes it holds, and its launch (certified precision; no workspace beyond the base)
+bool relu_shape_ok(const pg_net &n);
+int32_t launch_relu(const EvalParams &p, int dtype, hipStream_t s);
 
 
 }  // namespace pg

@@ -12,7 +12,8 @@
 //                         f64 argmax, the failures re-decided in f64 by the
 //                         wave itself (8-lane groups) or a service wave.
 //   k_general<WT>         any NETWORK_SHAPE, one wave per game, f64 numpy_nn
-//                         arithmetic with activations staged in LDS.
+//                         arithmetic with activations staged in LDS (sigmoid or ReLU).
+//   k_relu<LN,U,O,WT>     [6, H<=256, O] ReLU networks (pg_relu.hip).
 //   k_fitness             sum(all_rewards) / GAMES_TO_PLAY in the reference order.
 //   k_forward_*           NeuralNetwork.run batched (parity entry point).
 //   k_physics_*           the SoA Pong stepper on its own.
@@ -63,10 +64,12 @@ int32_t fail(int32_t code, const char *fmt, ...) {
 // [inputs..., 1], blas_dot); cur holds the input vector (with the trailing 1 if
 // bias).  Returns the argmax index; cur/nxt are LDS buffers of max_width + 1
 // doubles.  With z_all/h_all (pg_forward's diagnostics) every layer's
-// pre-activations and activations are stored there as well.
+// pre-activations and activations are stored there as well.  act: pg_activation
+// (numpy_nn.py:26) -- the sigmoid, or ReLU np.maximum(0.0, z) (numpy_nn.py:6-9:
+// NaN propagates, every z <= 0 gives 0), applied to every layer.
 template <typename WT>
 __device__ int forward_f64_wave(const WT *__restrict__ w, const int *nodes, int n_nodes, int b,
-                                double *&cur, double *&nxt, int lane, double *z_all = nullptr,
+                                double *&cur, double *&nxt, int lane, int act, double *z_all = nullptr,
                                 double *h_all = nullptr) {
   long off = 0;
   int zo = 0;
@@ -77,7 +80,7 @@ __device__ int forward_f64_wave(const WT *__restrict__ w, const int *nodes, int 
       const double *cv = cur;
       const double z = blas_dot([&](int i) { return (double)row[i]; }, [&](int i) { return cv[i]; }, cols,
                                 blas_kind(j, nout));
-      nxt[j] = sigmoid_f64(z);
+      nxt[j] = act == PG_ACT_RELU ? (!(z <= 0.0) ? z : 0.0) : sigmoid_f64(z);
       if (z_all) z_all[zo + j] = z;
       if (h_all) h_all[zo + j] = nxt[j];
     }
@@ -137,7 +140,7 @@ __global__ __launch_bounds__(64) void k_general(EvalParams p) {
             if (p.bias) cur[6] = 1.0;
           }
           wave_lds_sync();
-          left = index_to_code(forward_f64_wave(gl, p.nodes, p.n_nodes, p.bias, cur, nxt, lane));
+          left = index_to_code(forward_f64_wave(gl, p.nodes, p.n_nodes, p.bias, cur, nxt, lane, p.activation));
           wave_lds_sync();
           c_fwd += 1;
         } else if (kind == kOppScore) {
@@ -152,7 +155,7 @@ __global__ __launch_bounds__(64) void k_general(EvalParams p) {
           if (p.bias) cur[6] = 1.0;
         }
         wave_lds_sync();
-        right = index_to_code(forward_f64_wave(gr, p.nodes, p.n_nodes, p.bias, cur, nxt, lane));
+        right = index_to_code(forward_f64_wave(gr, p.nodes, p.n_nodes, p.bias, cur, nxt, lane, p.activation));
         wave_lds_sync();
         c_fwd += 1;
       }
@@ -209,7 +212,7 @@ struct FwdParams {
   int64_t gstride;
   int n;
   int nodes[PG_MAX_NODES];
-  int n_nodes, bias, max_width, n_units;
+  int n_nodes, bias, max_width, n_units, activation;
 };
 
 template <typename WT>
@@ -225,7 +228,7 @@ __global__ __launch_bounds__(64) void k_forward_general(FwdParams p) {
     for (int i = lane; i < n_in; i += 64) cur[i] = p.x[(long)t * n_in + i];
     if (p.bias && lane == 0) cur[n_in] = 1.0;
     wave_lds_sync();
-    const int idx = forward_f64_wave(gw, p.nodes, p.n_nodes, p.bias, cur, nxt, lane,
+    const int idx = forward_f64_wave(gw, p.nodes, p.n_nodes, p.bias, cur, nxt, lane, p.activation,
                                      p.z_all ? p.z_all + (long)t * p.n_units : nullptr,
                                      p.h_all ? p.h_all + (long)t * p.n_units : nullptr);
     if (lane == 0) p.index[t] = idx;
@@ -586,6 +589,8 @@ static int32_t check_net(const pg_net &n, bool game) {
   if (game && n.nodes[0] != 6)
     return fail(PG_ERR_INVALID, "the game feeds 6 inputs (utils.py:146-152); nodes[0]=%d", n.nodes[0]);
   if (n.dtype != PG_F32 && n.dtype != PG_F64) return fail(PG_ERR_INVALID, "net.dtype=%d", n.dtype);
+  if (n.activation != PG_ACT_SIGMOID && n.activation != PG_ACT_RELU)
+    return fail(PG_ERR_INVALID, "net.activation=%d (pg_activation: 0 sigmoid, 1 relu)", n.activation);
   if (gene_count(n) < 0) return fail(PG_ERR_INVALID, "network too large");
   return PG_OK;
 }
@@ -721,6 +726,8 @@ static size_t eval_base_workspace(const pg_eval_args *a) {
 // the kernel pg_eval_population runs for a (PG_KERNEL_AUTO resolved)
 static int resolve_kernel(const pg_eval_args *a) {
   if (a->kernel != PG_KERNEL_AUTO) return a->kernel;
+  if (a->net.activation == PG_ACT_RELU)  // k_relu's scope, else the general kernel (never SPLIT or WIDE)
+    return relu_shape_ok(a->net) && a->precision == PG_PREC_CERTIFIED ? PG_KERNEL_RELU : PG_KERNEL_GENERAL;
   if (resident_shape_ok(a->net) && a->precision == PG_PREC_CERTIFIED) return PG_KERNEL_SPLIT;
   if (wide_shape_ok(a->net, a->n_games) && (a->net.nodes[1] >= 64 || a->net.nodes[2] >= 64)) return PG_KERNEL_WIDE;
   return PG_KERNEL_GENERAL;
@@ -793,6 +800,15 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   if (a->trace && (a->trace_games < 0 || a->trace_cap < 1))
     return fail(PG_ERR_INVALID, "trace needs trace_games >= 0 and trace_cap >= 1");
   if (a->prep < PG_PREP_ALL || a->prep > PG_PREP_REST) return fail(PG_ERR_INVALID, "prep=%d", a->prep);
+  if (a->net.activation == PG_ACT_RELU) {  // ReLU networks: k_relu or k_general, whole episodes, no hard-case log
+    if (a->kernel == PG_KERNEL_SPLIT || a->kernel == PG_KERNEL_WIDE)
+      return fail(PG_ERR_UNSUPPORTED, "activation relu: the %s kernel evaluates sigmoid networks only (use RELU or GENERAL)",
+                  a->kernel == PG_KERNEL_SPLIT ? "split" : "wide");
+    if (a->horizon > 0) return fail(PG_ERR_UNSUPPORTED, "activation relu: no fixed-horizon mode (horizon must be 0)");
+    if (a->hard_log) return fail(PG_ERR_UNSUPPORTED, "activation relu: no hard-case log (hard_log must be NULL)");
+  } else if (a->kernel == PG_KERNEL_RELU) {
+    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu kernel evaluates PG_ACT_RELU networks only");
+  }
   if (a->horizon > 0 && a->trace) return fail(PG_ERR_INVALID, "horizon mode runs untraced (trace must be NULL)");
   if (a->horizon > 0 && resolve_kernel(a) != PG_KERNEL_SPLIT)
     return fail(PG_ERR_UNSUPPORTED, "horizon mode runs on the SPLIT kernel ([6, H<=64, 3], certified)");
@@ -833,6 +849,7 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   p.n_nodes = a->net.n_nodes;
   p.bias = a->net.bias ? 1 : 0;
   p.max_width = max_width(a->net);
+  p.activation = a->net.activation;
 
   p.prep = a->prep;
   p.horizon = a->horizon;
@@ -867,6 +884,12 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     // retired layouts (correct, measured slower than SPLIT; removed in round 4)
     return fail(PG_ERR_UNSUPPORTED, "the %s kernel was retired (DESIGN 4.1b-c); use SPLIT",
                 kernel == PG_KERNEL_RESIDENT ? "resident" : "staged");
+  } else if (kernel == PG_KERNEL_RELU) {
+    if (!relu_shape_ok(a->net))
+      return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
+    if (a->precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "relu kernel is the certified-precision path");
+    rc = launch_relu(p, a->net.dtype, s);
+    if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_GENERAL) {
     const size_t lds = 2 * (size_t)(p.max_width + 1) * sizeof(double);
     if (lds > 160 * 1024) return fail(PG_ERR_UNSUPPORTED, "layer width %d too large for LDS", p.max_width);
@@ -915,7 +938,9 @@ int32_t pg_forward(const pg_forward_args *a, void *stream) {
   p.n_nodes = a->net.n_nodes;
   p.bias = a->net.bias ? 1 : 0;
   p.max_width = max_width(a->net);
-  if (a->precision == PG_PREC_CERTIFIED && resident_shape_ok(a->net)) {
+  p.activation = a->net.activation;
+  // (ReLU networks: always the f64 forward below, whatever the precision)
+  if (a->precision == PG_PREC_CERTIFIED && resident_shape_ok(a->net) && a->net.activation == PG_ACT_SIGMOID) {
     const ResidentChoice c = choose_resident(a->net.nodes[1], 0);
     return a->net.dtype == PG_F64 ? launch_fwd_resident_any<double>(p, c, a->net.nodes[2], s)
                                   : launch_fwd_resident_any<float>(p, c, a->net.nodes[2], s);
@@ -938,6 +963,8 @@ int32_t pg_decide(const pg_decide_args *a, void *stream) {
   if (!a) return fail(PG_ERR_INVALID, "args is NULL");
   int32_t rc = check_net(a->net, false);
   if (rc != PG_OK) return rc;
+  if (a->net.activation != PG_ACT_SIGMOID)
+    return fail(PG_ERR_UNSUPPORTED, "pg_decide: activation relu -- the split kernel's cascade is the sigmoid's (pg_relu_decide)");
   if (!resident_shape_ok(a->net)) return fail(PG_ERR_UNSUPPORTED, "pg_decide: the split kernel's shapes only");
   if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);
   if (a->n == 0) return PG_OK;
@@ -983,6 +1010,8 @@ int32_t pg_wide_decide(const pg_wide_decide_args *a, void *stream) {
   if (!a) return fail(PG_ERR_INVALID, "args is NULL");
   int32_t rc = check_net(a->net, false);
   if (rc != PG_OK) return rc;
+  if (a->net.activation != PG_ACT_SIGMOID)
+    return fail(PG_ERR_UNSUPPORTED, "pg_wide_decide: activation relu -- the wide kernel evaluates sigmoid networks only");
   if (!wide_shape_ok(a->net, 1))
     return fail(PG_ERR_UNSUPPORTED, "pg_wide_decide: the wide kernel's shapes [6, H1<=512, H2<=512, 1..4] only");
   if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);

@@ -30,7 +30,29 @@ def sigmoid(x):
     return 1 / (1 + np.e ** -np.asarray(x, dtype=np.float64))
 
 
-activation_function = sigmoid
+def ReLU(x):
+    """np.maximum(0.0, x), the reference's "alternative activation function"
+    (numpy_nn.py:6-9), host-side helper."""
+    return np.maximum(0.0, np.asarray(x, dtype=np.float64))
+
+
+_ACTIVATIONS = {"sigmoid": sigmoid, "relu": ReLU}
+if config.ACTIVATION not in _ACTIVATIONS:
+    raise ValueError(f"config.ACTIVATION must be one of {sorted(_ACTIVATIONS)}, got {config.ACTIVATION!r}")
+# The reference's one-line switch (numpy_nn.py:26).  Rebinding it -- e.g.
+# ``numpy_nn.activation_function = numpy_nn.ReLU`` -- selects the device
+# activation of every later evaluation (resolved at call time, activation()).
+activation_function = _ACTIVATIONS[config.ACTIVATION]
+
+
+def activation() -> str:
+    """The device activation ("sigmoid" / "relu") ``activation_function`` is bound to."""
+    for name, fn in _ACTIVATIONS.items():
+        if activation_function is fn:
+            return name
+    raise NotImplementedError(
+        f"activation_function = {activation_function!r}: the device evaluates numpy_nn.sigmoid and "
+        "numpy_nn.ReLU only")
 
 
 class NeuralNetwork:
@@ -50,7 +72,7 @@ class NeuralNetwork:
 
     def _evaluator(self):
         return runtime.evaluator(self.nodes, bool(self.bias), genome_dtype="float64",
-                                 precision=config.PRECISION, device=config.DEVICE)
+                                 precision=config.PRECISION, device=config.DEVICE, activation=activation())
 
     def populate_weights(self, weights):
         """Slice the flat genome into per-layer (out, in + bias) matrices."""

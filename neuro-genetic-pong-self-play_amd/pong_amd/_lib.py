@@ -16,16 +16,18 @@ LIB_NAME = "libpong_ga.so"
 LIB_PATH = os.environ.get("PONG_GA_LIB") or os.path.join(PKG_DIR, LIB_NAME)  # override: variant builds
 HEADER_PATH = os.path.join(REPO_DIR, "include", "pong_ga.h")
 
-PG_ABI_VERSION = 12
+PG_ABI_VERSION = 13
 PG_MAX_NODES = 9
 
 PG_OK, PG_ERR_INVALID, PG_ERR_HIP, PG_ERR_UNSUPPORTED = 0, -1, -2, -3
 PG_F32, PG_F64 = 0, 1
+PG_ACT_SIGMOID, PG_ACT_RELU = 0, 1
 PG_OPP_HARDCODED, PG_OPP_ROM_CPU, PG_OPP_SCORE, PG_OPP_NN = 0, 1, 2, 3
 PG_PREP_ALL, PG_PREP_GENOMES, PG_PREP_REST = 0, 1, 2
 PG_PREC_CERTIFIED, PG_PREC_F64 = 0, 1
 PG_SCHED_REFERENCE, PG_SCHED_SELFPLAY = 0, 1
 PG_KERNEL_AUTO, PG_KERNEL_GENERAL, PG_KERNEL_RESIDENT, PG_KERNEL_SPLIT, PG_KERNEL_WIDE, PG_KERNEL_STAGED = 0, 1, 2, 3, 4, 5
+PG_KERNEL_RELU = 6
 PG_STATE_FIELDS = 16
 STATE_FIELD_NAMES = ("ball_x", "ball_y", "ball_vx", "ball_vy", "ball_visible", "serve_timer",
                      "serve_dir", "hits", "point", "lpy", "rpy", "score1", "score2",
@@ -36,7 +38,8 @@ _vp = ctypes.c_void_p
 
 class PgNet(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("nodes", ctypes.c_int32 * PG_MAX_NODES),
-                ("bias", ctypes.c_int32), ("dtype", ctypes.c_int32)]
+                ("bias", ctypes.c_int32), ("dtype", ctypes.c_int32),
+                ("activation", ctypes.c_int32)]  # ABI 13: pg_activation, 0 = sigmoid
 
 
 class PgEvalArgs(ctypes.Structure):
@@ -85,6 +88,13 @@ class PgWideDecideArgs(ctypes.Structure):
         ("net", PgNet), ("n", ctypes.c_int32), ("genomes", _vp), ("genome_stride", ctypes.c_int64),
         ("genome_index", _vp), ("k", _vp), ("index", _vp), ("act", _vp),
         ("workspace", _vp), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class PgReluDecideArgs(ctypes.Structure):
+    _fields_ = [
+        ("net", PgNet), ("n", ctypes.c_int32), ("genomes", _vp), ("genome_stride", ctypes.c_int64),
+        ("genome_index", _vp), ("k", _vp), ("index", _vp), ("stage", _vp), ("z32", _vp), ("bound", _vp),
     ]
 
 
@@ -197,6 +207,7 @@ SIGNATURES = {
     "pg_decide": (ctypes.c_int32, [ctypes.POINTER(PgDecideArgs), _vp]),
     "pg_wide_decide_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PgWideDecideArgs)]),
     "pg_wide_decide": (ctypes.c_int32, [ctypes.POINTER(PgWideDecideArgs), _vp]),
+    "pg_relu_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_physics_reset": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp, _vp]),
     "pg_physics_step": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp]),
     "pg_ga_select_tournament": (ctypes.c_int32, [ctypes.POINTER(PgSelectArgs), _vp]),
@@ -272,9 +283,9 @@ def check(func: str, rc: int) -> None:
         raise PongGAError(func, rc, msg.decode() if msg else "")
 
 
-def make_net(nodes, bias=True, dtype=PG_F64) -> PgNet:
+def make_net(nodes, bias=True, dtype=PG_F64, activation=PG_ACT_SIGMOID) -> PgNet:
     nodes = [int(n) for n in nodes]
     if not 2 <= len(nodes) <= PG_MAX_NODES:
         raise ValueError(f"NETWORK_SHAPE must have 2..{PG_MAX_NODES} entries, got {nodes}")
     arr = (ctypes.c_int32 * PG_MAX_NODES)(*(nodes + [0] * (PG_MAX_NODES - len(nodes))))
-    return PgNet(len(nodes), arr, 1 if bias else 0, dtype)
+    return PgNet(len(nodes), arr, 1 if bias else 0, dtype, int(activation))

@@ -88,11 +88,16 @@ def read_tensors(path: str, device=None, block_bytes: int = 1 << 28):
 
 
 def _config(ga) -> dict:
-    return {"nodes": ga.nodes, "population_size": ga.P, "hof_size": ga.H, "tournsize": ga.tournsize,
+    cfg = {"nodes": ga.nodes, "population_size": ga.P, "hof_size": ga.H, "tournsize": ga.tournsize,
             "bias": ga.bias, "dtype": str(ga.dtype).replace("torch.", ""), "n_games": ga.n_games,
             "schedule": ga.schedule, "cxpb": ga.cxpb, "mutpb": ga.mutpb, "alpha": ga.alpha, "mu": ga.mu,
             "sigma": ga.sigma, "indpb": ga.indpb, "seed": ga.seed, "physics_seed": ga.physics_seed,
             "precision": ga.precision, "kernel": ga.kernel, "hof_block_rows": ga.hof_block_rows}
+    # written only when it is not the default: a sigmoid run's config is what it
+    # always was, and a checkpoint without the key loads as sigmoid
+    if getattr(ga, "activation", "sigmoid") != "sigmoid":
+        cfg["activation"] = ga.activation
+    return cfg
 
 
 def save(ga, path: str) -> str:

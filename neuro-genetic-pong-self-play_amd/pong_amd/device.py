@@ -17,7 +17,8 @@ from . import _lib as L
 PRECISIONS = {"certified": L.PG_PREC_CERTIFIED, "f64": L.PG_PREC_F64}
 PREPS = {"all": L.PG_PREP_ALL, "genomes": L.PG_PREP_GENOMES, "rest": L.PG_PREP_REST}
 KERNELS = {"auto": L.PG_KERNEL_AUTO, "general": L.PG_KERNEL_GENERAL, "split": L.PG_KERNEL_SPLIT,
-           "wide": L.PG_KERNEL_WIDE}
+           "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU}
+ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
 
@@ -79,7 +80,9 @@ class Evaluator:
 
     def __init__(self, nodes, bias=True, dtype=torch.float64, device=None, n_games=6,
                  precision="certified", kernel="auto", group_lanes=0, seed=0, horizon=0,
-                 timeout_thresh=0, win_score=0):
+                 timeout_thresh=0, win_score=0, activation="sigmoid"):
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, got {activation!r}")
         if not torch.cuda.is_available():
             raise RuntimeError("pong_amd.Evaluator needs a HIP device (no CPU fallback)")
         L.lib()
@@ -100,7 +103,9 @@ class Evaluator:
         self.timeout_thresh = int(timeout_thresh)
         self.win_score = int(win_score)
         self.genes = gene_count(self.nodes, self.bias)
-        self.net = L.make_net(self.nodes, self.bias, DTYPES[dtype])
+        # pg_net.activation: numpy_nn's activation_function (numpy_nn.py:26), every layer
+        self.activation = activation
+        self.net = L.make_net(self.nodes, self.bias, DTYPES[dtype], ACTIVATIONS[activation])
         self._ws = None
         self._prep_key = self._prep_ws = None  # what the last prep="genomes" call left in the workspace
 
@@ -309,6 +314,41 @@ class Evaluator:
         with torch.cuda.device(dev):
             L.check("pg_decide", L.lib().pg_decide(ctypes.byref(a), _stream(dev)))
         return index, stage
+
+    def relu_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The ReLU kernel's own decision (pg_relu_decide) on doubled-centroid
+        features k [n, 6] int32: returns (argmax index [n] int32, stage [n]
+        int32: 0 decided by the f32 certificate, 1 recomputed in f64, z32
+        [n, out] f32 output pre-activations, bound [n] f32 on |z32 - z64|;
+        inf = the network is always decided in f64)."""
+        dev = self.device
+        _need(genomes, "genomes", self.dtype, dev)
+        if genomes.dim() != 2 or genomes.shape[1] < self.genes:
+            raise ValueError(f"genomes must be [n, >= {self.genes}], got {tuple(genomes.shape)}")
+        n = k.shape[0]
+        _need(k, "k", torch.int32, dev, (n, 6))
+        if genome_index is not None:
+            _need(genome_index, "genome_index", torch.int32, dev, (n,))
+            # one host sync: an out-of-range row would fault the GPU
+            if n and bool(((genome_index < 0) | (genome_index >= genomes.shape[0])).any()):
+                raise ValueError(f"genome_index must index the {genomes.shape[0]}-row genomes tensor")
+        elif n > genomes.shape[0]:
+            raise ValueError("more passes than genome rows (pass genome_index)")
+        index = torch.empty(n, dtype=torch.int32, device=dev)
+        stage = torch.empty(n, dtype=torch.int32, device=dev)
+        z32 = torch.empty((n, self.nodes[-1]), dtype=torch.float32, device=dev)
+        bound = torch.empty(n, dtype=torch.float32, device=dev)
+        a = L.PgReluDecideArgs()
+        a.net = self.net
+        a.n = n
+        a.genomes = _ptr(genomes)
+        a.genome_stride = genomes.stride(0) if genomes.shape[0] > 1 else genomes.shape[1]
+        a.genome_index = _ptr(genome_index)
+        a.k = _ptr(k)
+        a.index, a.stage, a.z32, a.bound = _ptr(index), _ptr(stage), _ptr(z32), _ptr(bound)
+        with torch.cuda.device(dev):
+            L.check("pg_relu_decide", L.lib().pg_relu_decide(ctypes.byref(a), _stream(dev)))
+        return index, stage, z32, bound
 
     def wide_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
         """k_wide's own decision (pg_wide_decide: one frame of the evaluation

@@ -65,7 +65,8 @@ class DeviceGA:
                  n_games: int = 6, schedule: str = "reference", cxpb: float = 0.9, mutpb: float = 0.9,
                  alpha: float = 0.9, mu: float = 0.0, sigma: float = 0.9, indpb: float = 0.9,
                  seed: int = 0, physics_seed: int = 0, precision: str = "certified", kernel: str = "auto",
-                 group=None, hof_block_rows: int = 0, timeout_thresh: int = 0, win_score: int = 0):
+                 group=None, hof_block_rows: int = 0, timeout_thresh: int = 0, win_score: int = 0,
+                 activation: str = "sigmoid"):
         if schedule not in D.SCHEDULES:
             raise ValueError(f"schedule must be one of {sorted(D.SCHEDULES)}")
         self.nodes = [int(v) for v in nodes]
@@ -77,7 +78,8 @@ class DeviceGA:
             raise ValueError("population_size >= 1, hof_size >= 0 and tournsize >= 1 required")
         self.ev = D.Evaluator(self.nodes, bias=bias, dtype=dtype, device=device, n_games=n_games,
                               precision=precision, kernel=kernel, seed=physics_seed,
-                              timeout_thresh=timeout_thresh, win_score=win_score)
+                              timeout_thresh=timeout_thresh, win_score=win_score, activation=activation)
+        self.activation = activation  # numpy_nn's activation_function (numpy_nn.py:26): "sigmoid" / "relu"
         self.device, self.dtype, self.G = self.ev.device, dtype, self.ev.genes
         self.bias, self.n_games, self.schedule = bool(bias), int(n_games), schedule
         self.cxpb, self.mutpb, self.alpha = float(cxpb), float(mutpb), float(alpha)

@@ -40,7 +40,8 @@ def _code_bits(code: np.ndarray, shift: int) -> np.ndarray:
 
 def replay(ev: D.Evaluator, genome: torch.Tensor, kind, opp, mult, opponents: Optional[torch.Tensor] = None,
            cap: int = 8192, every: int = 1):
-    """Play one genome's games with traces and re-render them.
+    """Play one genome's games with traces and re-render them (on ``ev``'s
+    kernel, precision and activation).
 
     Returns (EvalResult, frames): frames[g] is a uint8 array [F_g / every, 210,
     160, 3] of game g's frames (after each env.step).  The re-simulated final

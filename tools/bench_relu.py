@@ -1,0 +1,91 @@
+"""Measure Evaluator.evaluate alone on ReLU networks: k_relu against the general
+kernel (the only other way to run the workload), and the sigmoid k_service on
+the same genomes for context.  One JSON line per run.
+
+Workload: [6,64,3] networks, 6 self-play games per genome against a hall of
+pop // 4, genes N(0, 3) drawn as bench.py's default workload draws them
+(torch.randn from a device generator seeded with 1234 for the population and
+1235 for the hall, f64).  Each launch is timed between two device events on a
+quiet stream after warm-up launches; the median and the spread (min, max, the
+interquartile range) of >= 20 launches are reported.
+
+    python tools/bench_relu.py                      # the four runs
+    python tools/bench_relu.py --runs relu:4096 general:4096 --launches 30
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "neuro-genetic-pong-self-play_amd"))
+
+from pong_amd.device import Evaluator  # noqa: E402
+
+SHAPE = [6, 64, 3]
+RUNS = ["relu:4096", "general:4096", "relu:65536", "service:65536"]
+
+
+def workload(pop, dev, seed=1234, sigma=3.0):
+    G = sum((SHAPE[i] + 1) * SHAPE[i + 1] for i in range(len(SHAPE) - 1))
+    genomes = torch.randn((pop, G), generator=torch.Generator(device=dev).manual_seed(seed), dtype=torch.float64,
+                          device=dev).mul_(sigma)
+    hall = torch.randn((max(pop // 4, 1), G), generator=torch.Generator(device=dev).manual_seed(seed + 1),
+                       dtype=torch.float64, device=dev).mul_(sigma)
+    return genomes, hall
+
+
+def run(name, pop, dev, warmup, launches):
+    activation = "sigmoid" if name == "service" else "relu"
+    kernel = "split" if name == "service" else name
+    ev = Evaluator(SHAPE, device=dev, activation=activation, kernel=kernel,
+                   precision="f64" if name == "general" else "certified")
+    genomes, hall = workload(pop, dev)
+    sched = ev.selfplay_schedule(pop, hall.shape[0])
+    res = None
+    for _ in range(warmup):
+        res, _ = ev.evaluate(genomes, *sched, opponents=hall, out=res, validate=False)
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(launches):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        res, _ = ev.evaluate(genomes, *sched, opponents=hall, out=res, validate=False)
+        t1.record()
+        t1.synchronize()
+        ms.append(t0.elapsed_time(t1))
+    c = res.counters.cpu().numpy()
+    ms = np.array(ms)
+    med = float(np.median(ms))
+    q1, q3 = np.percentile(ms, [25, 75])
+    frames = int(res.frames.sum())
+    return {"kernel": {"relu": "k_relu", "general": "k_general", "service": "k_service"}[name], "activation": activation,
+            "shape": SHAPE, "pop": pop, "games": 6, "hall": int(hall.shape[0]), "launches": launches, "warmup": warmup,
+            "ms_median": round(med, 4), "ms_min": round(float(ms.min()), 4), "ms_max": round(float(ms.max()), 4),
+            "ms_iqr": round(float(q3 - q1), 4), "stepped_env_steps": int(c[0]), "episode_frames": frames,
+            "stepped_env_steps_per_s": round(int(c[0]) / (med * 1e-3), 1), "forwards": int(c[1]),
+            "f64_forwards": int(c[2]), "f64_share": round(int(c[2]) / max(int(c[1]), 1), 6),
+            "device": torch.cuda.get_device_name(dev)}
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, general, service")
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--launches", type=int, default=20)
+    args = p.parse_args()
+    if args.launches < 20:
+        p.error("--launches must be >= 20")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for spec in args.runs:
+        name, pop = spec.split(":")
+        if name not in ("relu", "general", "service"):
+            p.error(f"unknown kernel {name!r}")
+        print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches)), flush=True)
+
+
+if __name__ == "__main__":
+    main()

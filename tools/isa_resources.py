@@ -21,7 +21,8 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 TARGET = "gfx950"
 # kernels on the evaluation path (the rest are listed with --all)
-HOT = ("k_service<8, 16, 3", "k_prep_records<8, 16, 3", "k_wide<", "k_decide<4, 16, 3", "k_fitness", "k_merge",
+HOT = ("k_service<8, 16, 3", "k_prep_records<8, 16, 3", "k_wide<", "k_decide<4, 16, 3", "k_relu<4, 16, 3", "k_fitness",
+       "k_merge",
        "k_hof", "k_scatter", "k_order", "k_inherit", "k_iota", "k_cand_keys", "k_vary", "k_select", "k_schedule",
        "k_row_hash", "k_forward_general")
 
