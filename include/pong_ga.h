@@ -113,7 +113,7 @@ typedef enum pg_kernel {
   PG_KERNEL_SPLIT = 3      /* [6, H<=256, 2..4]: half a lane group per paddle's network; f32 forwards with
                               a certified argmax, the failures re-decided in f64 by the wave itself
                               (8-lane groups) or by one service wave per block (other layouts) */,
-  PG_KERNEL_WIDE = 4,      /* [6, H1<=512, H2<=512, 1..4]: one 512-thread workgroup per genome plays its
+  PG_KERNEL_WIDE = 4,      /* [6, 2<=H1<=512, 2<=H2<=512, 2..4]: one 512-thread workgroup per genome plays its
                               games (up to 6; more: balanced chunks of <= 6, one workgroup pass each)
                               in lockstep and streams W2 from HBM each frame
                               (numpy_nn's f64 order; AUTO picks it for H1 or H2 >= 64) */
@@ -272,7 +272,7 @@ typedef struct pg_decide_args {
 } pg_decide_args;
 
 /* The wide kernel's decision for given inputs: k_wide itself (the evaluation
- * kernel of [6, H1 <= 512, H2 <= 512, 1..4] networks, BASELINE config 5) runs
+ * kernel of [6, 2 <= H1 <= 512, 2 <= H2 <= 512, 2..4] networks, BASELINE config 5) runs
  * one frame of network row genome_index[i] (i if NULL) on the doubled
  * centroids k[i][0..5] -- its layer path and argmax exactly as in a game
  * (get_actions main.py:143-150, NeuralNetwork.run numpy_nn.py:120-137), so the

@@ -649,7 +649,7 @@ __device__ PG_SLOW_INLINE int forward_f64_group(const WT *__restrict__ g, int H,
     double w[7];
 #pragma unroll
     for (int i = 0; i < 7; ++i) w[i] = (i < 6 || b) ? (double)row[i] : 0.0;
-    lds[j] = pg_sigmoid_f64(blas_dot6(w, x, b));
+    lds[j] = pg_sigmoid_f64(blas_dot6(w, x, b, H));
   }
   double *w2 = lds + H;
   const WT *v = g + (long)H * cols;

@@ -501,8 +501,53 @@ __device__ __forceinline__ double sigmoid_f64(double z) { return pg_sigmoid_f64(
 //   0  j < 4 (n / 4):         s[i % 4] = fma(a_i, x_i, s[i % 4]); (s0 + s2) + (s1 + s3)
 //   1  the next 2 if n & 2:   s[i % 2] += a_i x_i (product rounded);  s0 + s1
 //   2  the last if n & 1:     s[i % 4] += a_i x_i;                    (s0 + s2) + (s1 + s3)
+//   3  n == 1: no dgemv at all.  numpy takes a one-row matrix times a vector
+//      as a dot product of two vectors (cblas_matrixproduct: cblas_ddot), so a
+//      layer of a single unit is summed in OpenBLAS ddot's order (blas_ddot).
 __host__ __device__ constexpr int blas_kind(int j, int n) {
-  return j < 4 * (n >> 2) ? 0 : (((n & 2) && j < 4 * (n >> 2) + 2) ? 1 : 2);
+  return n == 1 ? 3 : j < 4 * (n >> 2) ? 0 : (((n & 2) && j < 4 * (n >> 2) + 2) ? 1 : 2);
+}
+
+// np.dot of a one-row matrix: OpenBLAS ddot (x86-64 ddot.c with the Haswell /
+// SkylakeX micro-kernel, as numpy's OpenBLAS 0.3.29 runs it on AVX-512 hosts).
+// Elements below 32 * (m / 32): four 8-wide accumulators, element i into lane
+// i % 8 of accumulator (i / 8) % 4, fused; each is then folded (lane l + lane
+// l + 4) into one of four 4-wide accumulators, which take the next 16 elements
+// if m & 16 (element i into lane i % 4 of accumulator (i / 4) % 4, fused);
+// the four are added in order lane by lane, the lanes as (l0 + l2) + (l1 +
+// l3); the last m & 15 elements are fused onto that sum one by one.  Up to
+// m = 31 (a hidden unit of the game networks: m = 7) the vector width plays no
+// part.  Written one lane at a time: a cold path, a handful of registers.
+template <class AF, class XF>
+__device__ __forceinline__ double blas_ddot(AF a, XF x, int m) {
+  const int n32 = m & ~31, n16 = m & ~15;
+  double dot = 0.0;
+  if (n16) {
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;  // (no array: l is a run-time index)
+#pragma unroll 1
+    for (int l = 0; l < 4; ++l) {
+      double vl = 0.0;
+#pragma unroll 1
+      for (int q = 0; q < 4; ++q) {
+        double lo = 0.0, hi = 0.0;
+#pragma unroll 1
+        for (int i = 8 * q + l; i < n32; i += 32) {
+          lo = fma(a(i), x(i), lo);
+          hi = fma(a(i + 4), x(i + 4), hi);
+        }
+        double acc = __dadd_rn(lo, hi);
+        if (n16 > n32) acc = fma(a(n32 + 4 * q + l), x(n32 + 4 * q + l), acc);
+        vl = q ? __dadd_rn(vl, acc) : acc;
+      }
+      v0 = l == 0 ? vl : v0;
+      v1 = l == 1 ? vl : v1;
+      v2 = l == 2 ? vl : v2;
+      v3 = l == 3 ? vl : v3;
+    }
+    dot = __dadd_rn(__dadd_rn(v0, v2), __dadd_rn(v1, v3));
+  }
+  for (int i = n16; i < m; ++i) dot = fma(a(i), x(i), dot);
+  return dot;
 }
 
 // One block's partial sums (nb a multiple of 4) starting at element i0.
@@ -551,7 +596,14 @@ __device__ __forceinline__ double blas_tail(AF a, XF x, int i0, int m3, double y
 // A hidden unit of the game networks: np.dot over [x0..x5] (+ the bias weight
 // times 1.0 when b).  m = 6 or 7: one 4-element block -- the same
 // (p0 + p2) + (p1 + p3) for every kind -- then the 2- or 3-element tail.
-__device__ __forceinline__ double blas_dot6(const double w[7], const double x[6], int b) {
+// n = the layer's unit count: a single unit is kind 3 (ddot: one fused chain).
+__device__ __forceinline__ double blas_dot6(const double w[7], const double x[6], int b, int n) {
+  if (n == 1) {
+    double dot = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) dot = fma(w[i], x[i], dot);
+    return b ? fma(w[6], 1.0, dot) : dot;
+  }
   const double blk = __dadd_rn(__dadd_rn(__dmul_rn(w[0], x[0]), __dmul_rn(w[2], x[2])),
                                __dadd_rn(__dmul_rn(w[1], x[1]), __dmul_rn(w[3], x[3])));
   const double t = fma(w[4], x[4], __dmul_rn(w[5], x[5]));
@@ -561,6 +613,7 @@ __device__ __forceinline__ double blas_dot6(const double w[7], const double x[6]
 // y_j = np.dot(W, x)[j], a(i) = W[j][i], x(i) = x[i], i < m.
 template <class AF, class XF>
 __device__ __forceinline__ double blas_dot(AF a, XF x, int m, int kind) {
+  if (kind == 3) return blas_ddot(a, x, m);
   const int m3 = m & 3, m2 = (m & 2047) - m3;
   int m1 = m & ~3, nb = 2048, i0 = 0;
   double y = 0.0;

@@ -514,7 +514,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(EvalParams p) {
             double w[7];
 #pragma unroll
             for (int i = 0; i < 7; ++i) w[i] = (double)w1[c < NG ? 0 : 1 + c - NG][i];
-            h1[j * NC + c] = blas_dot6(w, feat + c * 8, b);
+            h1[j * NC + c] = blas_dot6(w, feat + c * 8, b, 2);  // (H1 >= 2: wide_shape_ok)
           }
 #pragma unroll 4
           for (int c = 0; c < NC; ++c) h1[j * NC + c] = sigmoid_f64(h1[j * NC + c]);
@@ -854,9 +854,11 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(EvalParams p) {
     atomicAdd((unsigned long long *)&p.counters[7], (unsigned long long)c_streams);
 }
 
+// (no layer of a single unit: numpy sums a one-row np.dot in another order,
+// blas_kind 3, which only the general kernel follows for these shapes)
 bool wide_shape_ok(const pg_net &n, int n_games) {
-  return n.n_nodes == 4 && n.nodes[0] == 6 && n.nodes[1] >= 1 && n.nodes[1] <= kWideThreads &&
-         n.nodes[2] >= 1 && n.nodes[2] <= kWideThreads && n.nodes[3] >= 1 && n.nodes[3] <= 4 &&
+  return n.n_nodes == 4 && n.nodes[0] == 6 && n.nodes[1] >= 2 && n.nodes[1] <= kWideThreads &&
+         n.nodes[2] >= 2 && n.nodes[2] <= kWideThreads && n.nodes[3] >= 2 && n.nodes[3] <= 4 &&
          n_games >= 1 && n_games <= 64;
 }
 

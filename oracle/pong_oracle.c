@@ -179,8 +179,44 @@ int or_gene_count(const or_net *net) {
  * y accumulates the blocks (y + block); then the tail: 1 element y = fma(a, x, y);
  * 2: y + fma(a0, x0, a1 x1); 3: y + fma(a2, x2, fma(a0, x0, a1 x1)).  That is the
  * x86-64 AVX2/FMA kernel numpy's OpenBLAS (0.3.29, DYNAMIC_ARCH) selects on
- * Haswell-class and later cores, checked against np.dot in tests/test_blas_order.py. */
+ * Haswell-class and later cores, checked against np.dot in tests/test_blas_order.py.
+ *
+ * n == 1 is no dgemv: numpy takes a one-row matrix times a vector as a dot
+ * product of two vectors (cblas_matrixproduct: cblas_ddot), so a layer of a
+ * single unit is summed in OpenBLAS ddot's order (x86-64 ddot.c with the
+ * Haswell / SkylakeX micro-kernel as it runs on AVX-512 hosts).  Elements below
+ * 32 * (m / 32): four 8-wide accumulators, element i into lane i % 8 of
+ * accumulator (i / 8) % 4, fused; each is folded (lane l + lane l + 4) into one
+ * of four 4-wide accumulators, which take the next 16 elements if m & 16
+ * (element i into lane i % 4 of accumulator (i / 4) % 4, fused); the four are
+ * added in order lane by lane, the lanes as (l0 + l2) + (l1 + l3); the last
+ * m & 15 elements are fused onto that sum one by one.  Up to m = 31 the vector
+ * width plays no part. */
+static double or_blas_ddot(const double *a, const double *x, int m) {
+  const int n32 = m & ~31, n16 = m & ~15;
+  double dot = 0.0;
+  if (n16) {
+    double v[4];
+    for (int l = 0; l < 4; ++l) {
+      for (int q = 0; q < 4; ++q) {
+        double lo = 0.0, hi = 0.0;
+        for (int i = 8 * q + l; i < n32; i += 32) {
+          lo = fma(a[i], x[i], lo);
+          hi = fma(a[i + 4], x[i + 4], hi);
+        }
+        double acc = lo + hi;
+        if (n16 > n32) acc = fma(a[n32 + 4 * q + l], x[n32 + 4 * q + l], acc);
+        v[l] = q ? v[l] + acc : acc;
+      }
+    }
+    dot = (v[0] + v[2]) + (v[1] + v[3]);
+  }
+  for (int i = n16; i < m; ++i) dot = fma(a[i], x[i], dot);
+  return dot;
+}
+
 double or_blas_dot(const double *a, const double *x, int m, int j, int n) {
+  if (n == 1) return or_blas_ddot(a, x, m);
   const int kind = j < 4 * (n >> 2) ? 0 : ((n & 2) && j < 4 * (n >> 2) + 2) ? 1 : 2;
   const int m3 = m & 3, m2 = (m & 2047) - m3;
   int m1 = m & ~3, nb = 2048, start = 0;

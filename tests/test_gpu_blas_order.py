@@ -41,7 +41,9 @@ def _host_sigmoid(tmp_path, z):
 
 @pytest.mark.parametrize("shape,bias,n_gen", [
     ([6, 64, 3], True, 64), ([6, 2, 2], True, 64), ([6, 8, 8, 3], True, 32), ([6, 7, 5, 2], True, 32),
-    ([6, 4, 2], False, 32), ([6, 3000, 2], True, 2), ([6, 512, 512, 3], True, 2)])
+    ([6, 4, 2], False, 32), ([6, 3000, 2], True, 2), ([6, 512, 512, 3], True, 2),
+    # layers of a single unit (np.dot of a one-row matrix is a ddot: blas_kind 3), m = 7, 6, 21, 41 and 2, 1
+    ([6, 1, 2], True, 64), ([6, 1, 3], False, 64), ([6, 20, 1, 3], True, 32), ([6, 40, 1, 1], True, 32)])
 def test_f64_layers_in_numpy_order(gpu, oracle, tmp_path, shape, bias, n_gen):
     from pong_amd.device import Evaluator
     rng = np.random.default_rng(sum(shape) + (0 if bias else 7))

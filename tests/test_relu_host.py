@@ -1,7 +1,9 @@
 """ReLU policy networks (ABI 13, activation_function = ReLU numpy_nn.py:6-9, 26)
 without a GPU: the ABI values, the validation and kernel resolution of
 pg_eval_population, k_relu's static f32 error bound (csrc/pg_relu_bound.h,
-compiled for the host with gcc) against an f32 emulation of the kernel's chain,
+compiled for the host with gcc) against an f32 emulation of the kernel's chain
+(tests/_relu_model.py: its once-rounded fma, the networks built to use up the
+bound, the tie networks the GPU tests decide by np.dot's last bit),
 the drop-in numpy_nn's activation switch and the checkpoint configuration."""
 import ctypes
 import inspect
@@ -13,10 +15,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from _relu_model import (RELU_CAP, TIE_CELLS, U32, _bounds, _fma32, _fma32_twice, _s_max, _z32, _z64, cap_net,
+                         systematic_net, tie_case, tie_sensitivity, tiny_net)
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "pong_ga.h")
-BOUND_HDR = os.path.join(REPO, "neuro-genetic-pong-self-play_amd", "csrc", "pg_relu_bound.h")
-U32 = 2.0 ** -24
 
 
 @pytest.fixture(scope="module")
@@ -85,81 +88,6 @@ def test_workspace_bytes_of_relu_calls(lib):
 
 
 # ----------------------------------------------------------------- bound ----
-def _relu_lanes(H):
-    return 4 if H <= 64 else (8 if H <= 128 else 16)
-
-
-def _bounds(tmp_path, nets):
-    """pg_relu_bound_genome of each (H, O, genes) through a stand-alone gcc program."""
-    src = tmp_path / "b.c"
-    src.write_text(f'#include <stdio.h>\n#include <stdlib.h>\n#include "{BOUND_HDR}"\n'
-                   "int main(int argc, char **argv){ FILE *f = fopen(argv[1], \"rb\"); int hdr[3];\n"
-                   " while (fread(hdr, sizeof(int), 3, f) == 3) { int H = hdr[0], O = hdr[1];\n"
-                   "  size_t G = (size_t)H * 7 + (size_t)O * (H + 1); double *g = malloc(G * sizeof(double));\n"
-                   "  if (fread(g, sizeof(double), G, f) != G) return 1;\n"
-                   "  printf(\"%a\\n\", (double)pg_relu_bound_genome(g, H, O, hdr[2])); free(g); }\n"
-                   " return 0; }\n")
-    exe = tmp_path / "b"
-    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-o", str(exe), str(src), "-lm"])
-    data = tmp_path / "nets.bin"
-    with open(data, "wb") as fh:
-        for H, O, g in nets:
-            fh.write(np.array([H, O, _relu_lanes(H) * 16], np.int32).tobytes())
-            fh.write(np.ascontiguousarray(g, np.float64).tobytes())
-    out = subprocess.run([str(exe), str(data)], capture_output=True, text=True, check=True).stdout.split()
-    return np.array([float.fromhex(v) for v in out])
-
-
-def _fma32(a, b, c):
-    """fl32(a * b + c): the product of two f32 is exact in f64, the sum is rounded to f64, then to f32."""
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
-
-
-def _z32(H, O, g, k):
-    """k_relu's f32 chain (pg_relu.hpp relu_z32) on doubled centroids k [m, 6]:
-    unit j = hl + LN u on lane hl, 16 units per lane in order, a pairwise tree
-    over the lanes (group_sum), then the output bias."""
-    LN, U = _relu_lanes(H), 16
-    w1 = g[: H * 7].reshape(H, 7).astype(np.float32)
-    w2 = g[H * 7:].reshape(O, H + 1).astype(np.float32)
-    x = k.astype(np.float32) * np.float32(0.003125)  # feat32
-    a = np.broadcast_to(w1[:, 6], (len(k), H)).copy()
-    for i in range(6):
-        a = _fma32(w1[None, :, i], x[:, i:i + 1], a)
-    h = np.zeros((len(k), LN * U), np.float32)
-    h[:, :H] = np.maximum(a, np.float32(0))
-    w2p = np.zeros((O, LN * U), np.float32)
-    w2p[:, :H] = w2[:, :H]
-    h, w2p = h.reshape(len(k), U, LN), w2p.reshape(O, U, LN)
-    z = np.empty((len(k), O), np.float32)
-    for o in range(O):
-        acc = np.zeros((len(k), LN), np.float32)
-        for u in range(U):
-            acc = _fma32(w2p[o, u][None, :], h[:, u, :], acc)
-        while acc.shape[1] > 1:
-            acc = acc[:, 0::2] + acc[:, 1::2]
-        z[:, o] = acc[:, 0] + w2[o, H]
-    return z
-
-
-def _z64(H, O, g, k):
-    """numpy_nn's f64 pre-activations (NeuralNetwork.run numpy_nn.py:126-131 with ReLU)."""
-    w1, w2 = g[: H * 7].reshape(H, 7), g[H * 7:].reshape(O, H + 1)
-    z = np.empty((len(k), O))
-    for t in range(len(k)):
-        a0 = np.ones(7)
-        a0[:6] = (k[t] / 2) / 160
-        a1 = np.ones(H + 1)
-        a1[:-1] = np.maximum(0.0, np.dot(w1, a0))
-        z[t] = np.dot(w2, a1)
-    return z
-
-
-def _s_max(H, O, g):
-    w1, w2 = np.abs(g[: H * 7].reshape(H, 7)), np.abs(g[H * 7:].reshape(O, H + 1))
-    return float((w2[:, :H] @ w1.sum(axis=1) + w2[:, H]).max())
-
-
 def test_bound_covers_the_f32_chain(tmp_path):
     """2 000 random networks: the emulated f32 outputs lie within the bound of
     numpy's f64 np.dot chain, and the bound is a small multiple of u max_o S_o."""
@@ -202,6 +130,127 @@ def test_bound_is_inf_for_weights_f32_cannot_hold(tmp_path):
     e = _bounds(tmp_path, nets)
     for (H, O, g), bound in zip(nets, e):
         assert np.isinf(bound) == (not np.isfinite(g).all() or np.abs(g).max() >= 1e30)
+
+
+# ------------------------------------------------- the model's exact fma ----
+def _midpoint_cases(rng, n):
+    """a * b an odd 25-bit integer (exact in f64, half-way between the two f32
+    neighbours p - 1 and p + 1) plus a c far below f64's last bit of it: the
+    f64 sum rounds to p itself, and the second rounding to f32 then goes to the
+    even neighbour whatever the sign of c."""
+    a = (rng.integers(1 << 11, 1 << 12, n) | 1).astype(np.float32)
+    b = (rng.integers(1 << 12, 1 << 13, n) | 1).astype(np.float32)
+    keep = a.astype(np.int64) * b.astype(np.int64) >= 1 << 24
+    a, b = a[keep], b[keep]
+    c = (np.where(rng.random(len(a)) < 0.5, -1.0, 1.0) * 2.0 ** -rng.integers(40, 100, len(a))).astype(np.float32)
+    want = (a.astype(np.int64) * b.astype(np.int64) + np.sign(c).astype(np.int64)).astype(np.float32)
+    return a, b, c, want
+
+
+def test_model_fma_is_rounded_once(tmp_path):
+    rng = np.random.default_rng(21)
+    a, b, c, want = _midpoint_cases(rng, 4000)
+    assert len(a) > 1000
+    np.testing.assert_array_equal(_fma32(a, b, c), want)
+    wrong = _fma32_twice(a, b, c) != want
+    assert 0.25 < wrong.mean() < 0.75, wrong.mean()  # the twice-rounded formula: wrong whenever c points away from even
+    # the same, scaled into f32's subnormals (the last rounding is coarser there, not finer)
+    tiny = np.float32(2.0 ** -140)
+    sub = _fma32(a * np.float32(2.0 ** -12), b * tiny, np.float32(2.0 ** -149))
+    np.testing.assert_array_equal(sub, ((a.astype(np.float64) * b.astype(np.float64) * 2.0 ** -152 + 2.0 ** -149)
+                                        .astype(np.float32)))  # (that f64 sum is exact: < 53 bits)
+    # against the C library's fmaf on the hard cases and on random operands of every scale, inf and NaN included
+    ra = (rng.standard_normal(20000) * 2.0 ** rng.integers(-60, 60, 20000)).astype(np.float32)
+    rb = (rng.standard_normal(20000) * 2.0 ** rng.integers(-60, 60, 20000)).astype(np.float32)
+    rc = np.where(rng.random(20000) < 0.5, -(ra.astype(np.float64) * rb.astype(np.float64)) * (1 + 2.0 ** -rng.integers(1, 40, 20000)),
+                  rng.standard_normal(20000) * 2.0 ** rng.integers(-120, 120, 20000)).astype(np.float32)
+    ra[:4], rb[:4], rc[:4] = [np.inf, np.inf, np.nan, 0.0], [1.0, 0.0, 1.0, -1.0], [-np.inf, 1.0, 1.0, 0.0]
+    A, B, C = (np.concatenate(v) for v in ((a, ra), (b, rb), (c, rc)))
+    src = tmp_path / "f.c"
+    src.write_text("#include <math.h>\n#include <stdio.h>\n"
+                   "int main(int argc, char **argv){ FILE *f = fopen(argv[1], \"rb\"), *o = fopen(argv[2], \"wb\"); float v[3];\n"
+                   " while (fread(v, sizeof(float), 3, f) == 3) { volatile float r = fmaf(v[0], v[1], v[2]);\n"
+                   "  float w = r; fwrite(&w, sizeof(float), 1, o); }\n fclose(o); return 0; }\n")
+    exe = tmp_path / "f"
+    subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-o", str(exe), str(src), "-lm"])
+    np.stack([A, B, C], axis=1).astype(np.float32).tofile(tmp_path / "in.bin")
+    subprocess.check_call([str(exe), str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+    ref = np.fromfile(tmp_path / "out.bin", np.float32)
+    got = _fma32(A, B, C)
+    assert len(ref) == len(got)
+    nan = np.isnan(ref)
+    np.testing.assert_array_equal(np.isnan(got), nan)
+    np.testing.assert_array_equal(got[~nan].view(np.int32), ref[~nan].view(np.int32))
+    assert (_fma32_twice(A, B, C)[~nan] != ref[~nan]).any()
+
+
+# ------------------------------------ the bound on adversarial networks ----
+BOUND_H = (1, 64, 65, 128, 129, 256)
+
+
+def _family_nets():
+    """(family, H, O, genes) of the networks built to use up the bound."""
+    rng = np.random.default_rng(31)
+    for H in BOUND_H:
+        for O in (2, 3, 4):
+            yield "systematic", H, O, systematic_net(H, O)
+            yield "cap", H, O, cap_net(H, O, RELU_CAP * (1 - 1e-3))
+            yield "tiny", H, O, tiny_net(H, O, rng)
+
+
+def test_bound_covers_the_chain_on_adversarial_networks(tmp_path):
+    """The exact-fma model on networks whose roundings all point one way
+    (systematic_net), that sit just below PG_RELU_CAP, and whose genes are f32
+    subnormals or flush to zero: |z32 - z64| <= bound on all-0, all-320 and
+    random inputs, and z32 is finite whenever the bound is.  The printed ratio
+    err / (u max_o S_o) is the slack the derivation's 33 leaves (a measurement,
+    not a condition)."""
+    rng = np.random.default_rng(32)
+    fam = list(_family_nets())
+    e = _bounds(tmp_path, [(H, O, g) for _, H, O, g in fam])
+    assert np.isfinite(e).all() and (e > 0).all()
+    worst = {}
+    for (name, H, O, g), bound in zip(fam, e):
+        k = np.concatenate([np.zeros((1, 6), np.int64), np.full((1, 6), 320), rng.integers(0, 321, size=(14, 6))])
+        z32, z64 = _z32(H, O, g, k), _z64(H, O, g, k)
+        assert np.isfinite(z32).all(), (name, H, O)
+        err = np.abs(z32.astype(np.float64) - z64).max()
+        assert err <= bound, (name, H, O, err, bound)
+        s = _s_max(H, O, g)
+        if name == "cap":
+            assert RELU_CAP * (1 - 2e-3) < s < RELU_CAP
+        else:
+            assert (g > 0).all() if name == "systematic" else s < 1e-30
+        w = worst.setdefault(name, [0.0, 0.0])
+        w[0], w[1] = max(w[0], err / (U32 * s)), max(w[1], err / bound)
+    assert set(worst) == {"systematic", "cap", "tiny"}
+    for name, w in worst.items():  # (tiny_net's bound is its underflow term: u max S_o says nothing there)
+        print(f"largest |z32 - z64| / (u max S_o), {name}_net: {w[0]:.3f} (the bound: 33); / bound: {w[1]:.4f}")
+
+
+def test_bound_is_inf_just_above_the_cap(tmp_path):
+    nets = [(H, O, cap_net(H, O, RELU_CAP * (1 + d))) for H in BOUND_H for O in (2, 3, 4) for d in (1e-3, -1e-3)]
+    e = _bounds(tmp_path, nets)
+    for (H, O, g), bound in zip(nets, e):
+        assert np.isfinite(g.astype(np.float32)).all()
+        assert np.isinf(bound) == (_s_max(H, O, g) > RELU_CAP), (H, O, bound)
+    assert np.isinf(e[0::2]).all() and np.isfinite(e[1::2]).all()
+
+
+# ------------------------------------------------------- the tie networks ----
+@pytest.mark.parametrize("H,O", TIE_CELLS)
+def test_tie_net_is_sensitive_to_the_summation_order(H, O):
+    """numpy's own np.dot on the tie network of each cell the GPU test uses: the
+    exactly equal outputs come out bitwise different in at least 8 of 256
+    passes and np.argmax is non-zero at least once -- an f64 fallback that sums
+    in another order than np.dot cannot reproduce these decisions by luck."""
+    g, k = tie_case(H, O)
+    w1, w2 = g[: H * 7].reshape(H, 7), g[H * 7:].reshape(O, H + 1)
+    assert (w1[1::2] == w1[0:2 * (H // 2):2]).all() and (w2 >= 0).all() and (w2[:, H] > 0).all()
+    assert all((np.sort(w2[o]) == np.sort(w2[0])).all() and (w2[o] != w2[0]).any() for o in range(1, O))
+    assert (g.astype(np.float32) == g).all()
+    differ, nonzero = tie_sensitivity(H, O, g, k)
+    assert differ >= 8 and nonzero >= 1, (differ, nonzero)
 
 
 # --------------------------------------------------------------- drop-in ----
