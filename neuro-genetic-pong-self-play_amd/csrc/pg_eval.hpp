@@ -59,7 +59,7 @@ struct EvalParams {
   const int32_t *wide_probe_k;
   int32_t *wide_probe_index;  // out [n_genomes] np.argmax
   double *wide_probe_act;     // optional out [n_genomes, nodes[3]]
-  int activation;             // pg_net.activation (k_general, k_relu)
+  int activation;             // pg_net.activation (k_general, k_relu, k_relu2)
 };
 
 // Genome blocks / games this launch plays (pg_eval_args.n_active).  Made
@@ -156,6 +156,11 @@ int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s
 // shapes it holds, and its launch (certified precision; no workspace beyond the base)
 bool relu_shape_ok(const pg_net &n);
 int32_t launch_relu(const EvalParams &p, int dtype, hipStream_t s);
+
+// [6, 2..64, 2..64, 2..4] ReLU networks with bias on k_relu2 (pg_relu2.hip): the
+// same for two hidden layers
+bool relu2_shape_ok(const pg_net &n);
+int32_t launch_relu2(const EvalParams &p, int dtype, hipStream_t s);
 
 
 }  // namespace pg

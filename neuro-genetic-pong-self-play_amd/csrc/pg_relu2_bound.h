@@ -1,0 +1,147 @@
+/* pg_relu2_bound.h -- the static f32 error bound of k_relu2's certificate
+ * (pg_relu2.hpp), in plain C so that it compiles for the device and for the
+ * host alike (tests/test_relu2_host.py runs it under gcc).
+ *
+ * The network [6, H1, H2, O] with bias, inputs x_i = k_i / 320 in [0, 1]:
+ *   z1_j = sum_i W1_ji x_i + b1_j,   h1_j = max(0, z1_j)
+ *   z2_k = sum_j W2_kj h1_j + b2_k,  h2_k = max(0, z2_k)
+ *   z_o  = sum_k W3_ok h2_k + b3_o.
+ * The derivation does not depend on the order of any sum: if every term of a
+ * computed dot product passes through at most c roundings (factors 1 + d,
+ * |d| <= u = 2^-24), the result is sum_i t_i (1 + theta_i) with |theta_i| <=
+ * gamma_c = c u / (1 - c u), so it differs from the exact sum by at most
+ * gamma_c sum_i |t_i|, whatever the order.  The three chain lengths:
+ *
+ *   layer 1  PG_RELU2_CHAIN1 = 9:   1 (gene to f32) + 2 (the feature
+ *            fl32(k * fl32(1 / 320)), feat32) + 6 fused multiply-adds
+ *   layer 2  PG_RELU2_CHAIN2 = 65:  1 (gene) + one fused multiply-add per
+ *            (padded) layer-1 unit, <= 64, onto the bias
+ *   layer 3  PG_RELU2_CHAIN3 = 11:  1 (gene) + a lane's <= 4 units + the sum
+ *            over <= 32 lanes (5 steps) + the bias
+ * (pg_relu2.hpp asserts that every instantiated layout stays within them).
+ *
+ * With  A_j = sum_i |W1_ji| + |b1_j|           (>= |z1_j|, as x_i <= 1)
+ *       B_k = sum_j |W2_kj| A_j + |b2_k|       (>= |z2_k|)
+ *       S_o = sum_k |W3_ok| B_k + |b3_o|
+ * and ReLU exact and 1-Lipschitz:
+ *   |h1^_j - h1_j| <= gamma_9 A_j
+ *   |z2^_k - z2_k| <= sum_j |W2_kj| (gamma_9 A_j (1 + gamma_65) + gamma_65 A_j) + gamma_65 |b2_k|
+ *                  <= gamma_74 B_k      (gamma_a + gamma_b + gamma_a gamma_b <= gamma_(a+b))
+ *   |z^_o - z_o|   <= sum_k |W3_ok| (gamma_74 B_k (1 + gamma_11) + gamma_11 B_k) + gamma_11 |b3_o|
+ *                  <= gamma_85 S_o.
+ * numpy's own f64 result differs from the exact z_o by its three np.dot calls'
+ * and the features' roundings: < 2^-40 S_o, i.e. < 2^-16 u S_o.  The bound kept:
+ *   e = (K u max_o S_o + underflow) (1 + 2^-20),   K = PG_RELU2_K = 9 + 65 + 11 + 2 = 87:
+ * two u of slack for gamma_85 - 85 u (< 10^-3 u), the f64 part and the f64
+ * rounding of S_o itself (sums of non-negative terms: relative error below
+ * 2^-40 whatever the order, the lanes' partial sums and the host's serial loop
+ * alike), and 2^-20 for the conversion of e to f32.
+ * Underflow.  The above holds for normal results.  Every operation whose
+ * result is subnormal or flushed to zero adds at most eta = 2^-126:
+ *   a layer-1 unit: 7 gene conversions and 6 fmas, <= 13 eta (1 + u) in h1^_j;
+ *   a layer-2 unit: those through |W2^_kj|, a flushed W2 gene times its h1^_j
+ *     (<= eta (1 + gamma_9) A_j + ...), the bias conversion and 64 fmas:
+ *     E2_k <= eta (14 sum_j |W2_kj| + 2 sum_j A_j + 67);
+ *   an output: E2_k through |W3^_ok|, a flushed W3 gene times its h2^_k, the
+ *     <= 11 operations of the layer-3 chain:
+ *   underflow = eta (15 max_o T_o + (2 sum_j A_j + 68) max_o sum_k |W3_ok| + 2 sum_k B_k + 16),
+ *     T_o = sum_k |W3_ok| sum_j |W2_kj|.
+ * (A feature k_i * fl32(1/320) is 0 or >= 2^-9: never subnormal.)
+ * Overflow.  With sum_j A_j, sum_kj |W2_kj|, sum_k B_k, sum_k |W3_ok|, T_o and
+ * S_o all <= PG_RELU_CAP = 1e25 (sums of absolute values: NaN and inf
+ * propagate into them and fail the test) every gene converts to a finite f32
+ * and no intermediate exceeds B_k or S_o times (1 + gamma) < FLT_MAX, so z^ is
+ * finite.  Otherwise e = inf: the certificate never decides and the f64 path
+ * (numpy's semantics, NaN rule included) does.
+ */
+#ifndef PG_RELU2_BOUND_H
+#define PG_RELU2_BOUND_H
+
+#include <math.h>
+
+#include "pg_relu_bound.h" /* PG_HD, PG_RELU_CAP, PG_RELU_MAX_OUT */
+
+#define PG_RELU2_MAX_H 64
+#define PG_RELU2_CHAIN1 9  /* gene + feature (2) + 6 fmas */
+#define PG_RELU2_CHAIN2 65 /* gene + <= 64 fmas */
+#define PG_RELU2_CHAIN3 11 /* gene + <= 4 fmas + <= 5 lane-sum steps + bias */
+#define PG_RELU2_K ((double)(PG_RELU2_CHAIN1 + PG_RELU2_CHAIN2 + PG_RELU2_CHAIN3 + 2))
+
+/* Sums over (a share of) the layer-2 units; shares add field by field. */
+typedef struct pg_relu2_sums {
+  double S[PG_RELU_MAX_OUT];  /* sum_k |W3_ok| B_k */
+  double T[PG_RELU_MAX_OUT];  /* sum_k |W3_ok| sum_j |W2_kj| */
+  double W3[PG_RELU_MAX_OUT]; /* sum_k |W3_ok| */
+  double B;                   /* sum_k B_k */
+  double W2;                  /* sum_kj |W2_kj| */
+} pg_relu2_sums;
+
+PG_HD void pg_relu2_sums_init(pg_relu2_sums *s) {
+  for (int o = 0; o < PG_RELU_MAX_OUT; ++o) s->S[o] = s->T[o] = s->W3[o] = 0.0;
+  s->B = s->W2 = 0.0;
+}
+
+/* A_j of one layer-1 unit: its 6 input weights and its bias weight. */
+PG_HD double pg_relu2_unit1(const double w1[7]) {
+  double a = 0.0;
+  for (int i = 0; i < 7; ++i) a += fabs(w1[i]);
+  return a;
+}
+
+/* One layer-2 unit: b = B_k and w = sum_j |W2_kj| of its row, w3 its O output weights. */
+PG_HD void pg_relu2_sums_unit2(pg_relu2_sums *s, double b, double w, const double *w3, int O) {
+  for (int o = 0; o < O; ++o) {
+    s->S[o] += fabs(w3[o]) * b;
+    s->T[o] += fabs(w3[o]) * w;
+    s->W3[o] += fabs(w3[o]);
+  }
+  s->B += b;
+  s->W2 += w;
+}
+
+/* The bound from the sums over all layer-2 units, asum = sum_j A_j and the output biases c. */
+PG_HD float pg_relu2_bound_finish(const pg_relu2_sums *s, double asum, const double *c, int O) {
+  double smax = 0.0, tmax = 0.0, w3max = 0.0;
+  int ok = asum <= PG_RELU_CAP && s->B <= PG_RELU_CAP && s->W2 <= PG_RELU_CAP; /* false for NaN */
+  for (int o = 0; o < O; ++o) {
+    const double so = s->S[o] + fabs(c[o]);
+    ok = ok && so <= PG_RELU_CAP && s->T[o] <= PG_RELU_CAP && s->W3[o] <= PG_RELU_CAP;
+    smax = so > smax ? so : smax;
+    tmax = s->T[o] > tmax ? s->T[o] : tmax;
+    w3max = s->W3[o] > w3max ? s->W3[o] : w3max;
+  }
+  if (!ok) return (float)INFINITY;
+  const double u = 0x1.0p-24, eta = 0x1.0p-126;
+  const double under = eta * (15.0 * tmax + (2.0 * asum + 68.0) * w3max + 2.0 * s->B + 16.0);
+  return (float)((PG_RELU2_K * u * smax + under) * (1.0 + 0x1.0p-20));
+}
+
+/* The whole bound of one genome (numpy_nn.py:52-69 layout with bias: W1
+ * [H1, 7], W2 [H2, H1 + 1], W3 [O, H2 + 1], bias columns last), serially:
+ * what a test or a host tool calls; k_relu2's lanes run the same functions on
+ * their shares.  H1 <= PG_RELU2_MAX_H. */
+PG_HD float pg_relu2_bound_genome(const double *g, int H1, int H2, int O) {
+  double A[PG_RELU2_MAX_H], asum = 0.0, c[PG_RELU_MAX_OUT];
+  const double *w2 = g + (long)H1 * 7, *w3 = w2 + (long)H2 * (H1 + 1);
+  pg_relu2_sums s;
+  pg_relu2_sums_init(&s);
+  for (int j = 0; j < H1; ++j) {
+    A[j] = pg_relu2_unit1(g + (long)j * 7);
+    asum += A[j];
+  }
+  for (int k = 0; k < H2; ++k) {
+    const double *row = w2 + (long)k * (H1 + 1);
+    double b = 0.0, w = 0.0, v[PG_RELU_MAX_OUT];
+    for (int j = 0; j < H1; ++j) {
+      b += fabs(row[j]) * A[j];
+      w += fabs(row[j]);
+    }
+    b += fabs(row[H1]);
+    for (int o = 0; o < O; ++o) v[o] = w3[(long)o * (H2 + 1) + k];
+    pg_relu2_sums_unit2(&s, b, w, v, O);
+  }
+  for (int o = 0; o < O; ++o) c[o] = w3[(long)o * (H2 + 1) + H2];
+  return pg_relu2_bound_finish(&s, asum, c, O);
+}
+
+#endif /* PG_RELU2_BOUND_H */

@@ -14,6 +14,7 @@
 //   k_general<WT>         any NETWORK_SHAPE, one wave per game, f64 numpy_nn
 //                         arithmetic with activations staged in LDS (sigmoid or ReLU).
 //   k_relu<LN,U,O,WT>     [6, H<=256, O] ReLU networks (pg_relu.hip).
+//   k_relu2<LN,U1,U2,O,WT>  [6, H1<=64, H2<=64, O] ReLU networks (pg_relu2.hip).
 //   k_fitness             sum(all_rewards) / GAMES_TO_PLAY in the reference order.
 //   k_forward_*           NeuralNetwork.run batched (parity entry point).
 //   k_physics_*           the SoA Pong stepper on its own.
@@ -726,8 +727,10 @@ static size_t eval_base_workspace(const pg_eval_args *a) {
 // the kernel pg_eval_population runs for a (PG_KERNEL_AUTO resolved)
 static int resolve_kernel(const pg_eval_args *a) {
   if (a->kernel != PG_KERNEL_AUTO) return a->kernel;
-  if (a->net.activation == PG_ACT_RELU)  // k_relu's scope, else the general kernel (never SPLIT or WIDE)
-    return relu_shape_ok(a->net) && a->precision == PG_PREC_CERTIFIED ? PG_KERNEL_RELU : PG_KERNEL_GENERAL;
+  if (a->net.activation == PG_ACT_RELU) {  // k_relu's or k_relu2's scope, else the general kernel (never SPLIT or WIDE)
+    if (a->precision != PG_PREC_CERTIFIED) return PG_KERNEL_GENERAL;
+    return relu_shape_ok(a->net) ? PG_KERNEL_RELU : (relu2_shape_ok(a->net) ? PG_KERNEL_RELU2 : PG_KERNEL_GENERAL);
+  }
   if (resident_shape_ok(a->net) && a->precision == PG_PREC_CERTIFIED) return PG_KERNEL_SPLIT;
   if (wide_shape_ok(a->net, a->n_games) && (a->net.nodes[1] >= 64 || a->net.nodes[2] >= 64)) return PG_KERNEL_WIDE;
   return PG_KERNEL_GENERAL;
@@ -781,6 +784,13 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   if (a->timeout_thresh != 0 && (a->timeout_thresh < 32 || a->timeout_thresh > (1 << 20)))
     return fail(PG_ERR_INVALID, "timeout_thresh=%d not 0 or in [32, 1048576]", a->timeout_thresh);
   if (a->win_score < 0) return fail(PG_ERR_INVALID, "win_score=%d < 0", a->win_score);
+  if (a->kernel == PG_KERNEL_RELU2) {  // its scope is checked even for an empty launch
+    if (a->net.activation != PG_ACT_RELU)
+      return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu2 kernel evaluates PG_ACT_RELU networks only");
+    if (!relu2_shape_ok(a->net))
+      return fail(PG_ERR_UNSUPPORTED, "relu2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4] with bias");
+    if (a->precision == PG_PREC_F64) return fail(PG_ERR_UNSUPPORTED, "relu2 kernel is the certified-precision path");
+  }
   if (a->n_genomes == 0) {  // nothing to play (e.g. an empty shard); the counters still read zero
     if (a->counters) PG_HIP(hipMemsetAsync(a->counters, 0, 16 * sizeof(uint64_t), (hipStream_t)stream));
     return PG_OK;
@@ -800,9 +810,9 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   if (a->trace && (a->trace_games < 0 || a->trace_cap < 1))
     return fail(PG_ERR_INVALID, "trace needs trace_games >= 0 and trace_cap >= 1");
   if (a->prep < PG_PREP_ALL || a->prep > PG_PREP_REST) return fail(PG_ERR_INVALID, "prep=%d", a->prep);
-  if (a->net.activation == PG_ACT_RELU) {  // ReLU networks: k_relu or k_general, whole episodes, no hard-case log
+  if (a->net.activation == PG_ACT_RELU) {  // ReLU networks: k_relu, k_relu2 or k_general, whole episodes, no hard-case log
     if (a->kernel == PG_KERNEL_SPLIT || a->kernel == PG_KERNEL_WIDE)
-      return fail(PG_ERR_UNSUPPORTED, "activation relu: the %s kernel evaluates sigmoid networks only (use RELU or GENERAL)",
+      return fail(PG_ERR_UNSUPPORTED, "activation relu: the %s kernel evaluates sigmoid networks only (use RELU, RELU2 or GENERAL)",
                   a->kernel == PG_KERNEL_SPLIT ? "split" : "wide");
     if (a->horizon > 0) return fail(PG_ERR_UNSUPPORTED, "activation relu: no fixed-horizon mode (horizon must be 0)");
     if (a->hard_log) return fail(PG_ERR_UNSUPPORTED, "activation relu: no hard-case log (hard_log must be NULL)");
@@ -889,6 +899,9 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
       return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
     if (a->precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "relu kernel is the certified-precision path");
     rc = launch_relu(p, a->net.dtype, s);
+    if (rc != PG_OK) return rc;
+  } else if (kernel == PG_KERNEL_RELU2) {  // (activation, shape and precision were checked on entry)
+    rc = launch_relu2(p, a->net.dtype, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_GENERAL) {
     const size_t lds = 2 * (size_t)(p.max_width + 1) * sizeof(double);

@@ -17,7 +17,7 @@ from . import _lib as L
 PRECISIONS = {"certified": L.PG_PREC_CERTIFIED, "f64": L.PG_PREC_F64}
 PREPS = {"all": L.PG_PREP_ALL, "genomes": L.PG_PREP_GENOMES, "rest": L.PG_PREP_REST}
 KERNELS = {"auto": L.PG_KERNEL_AUTO, "general": L.PG_KERNEL_GENERAL, "split": L.PG_KERNEL_SPLIT,
-           "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU}
+           "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU, "relu2": L.PG_KERNEL_RELU2}
 ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
@@ -321,6 +321,14 @@ class Evaluator:
         int32: 0 decided by the f32 certificate, 1 recomputed in f64, z32
         [n, out] f32 output pre-activations, bound [n] f32 on |z32 - z64|;
         inf = the network is always decided in f64)."""
+        return self._relu_decide("pg_relu_decide", genomes, k, genome_index)
+
+    def relu2_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The same for the two-hidden-layer ReLU kernel (pg_relu2_decide:
+        k_relu2's decision code, [6, 2..64, 2..64, 2..4] networks with bias)."""
+        return self._relu_decide("pg_relu2_decide", genomes, k, genome_index)
+
+    def _relu_decide(self, entry: str, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor]):
         dev = self.device
         _need(genomes, "genomes", self.dtype, dev)
         if genomes.dim() != 2 or genomes.shape[1] < self.genes:
@@ -347,7 +355,7 @@ class Evaluator:
         a.k = _ptr(k)
         a.index, a.stage, a.z32, a.bound = _ptr(index), _ptr(stage), _ptr(z32), _ptr(bound)
         with torch.cuda.device(dev):
-            L.check("pg_relu_decide", L.lib().pg_relu_decide(ctypes.byref(a), _stream(dev)))
+            L.check(entry, getattr(L.lib(), entry)(ctypes.byref(a), _stream(dev)))
         return index, stage, z32, bound
 
     def wide_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):

@@ -11,6 +11,7 @@ interquartile range) of >= 20 launches are reported.
 
     python tools/bench_relu.py                      # the four runs
     python tools/bench_relu.py --runs relu:4096 general:4096 --launches 30
+    python tools/bench_relu.py --shape 6 64 64 3 --runs relu2:4096 general:4096   # k_relu2
 """
 import argparse
 import json
@@ -29,8 +30,8 @@ SHAPE = [6, 64, 3]
 RUNS = ["relu:4096", "general:4096", "relu:65536", "service:65536"]
 
 
-def workload(pop, dev, seed=1234, sigma=3.0):
-    G = sum((SHAPE[i] + 1) * SHAPE[i + 1] for i in range(len(SHAPE) - 1))
+def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE):
+    G = sum((shape[i] + 1) * shape[i + 1] for i in range(len(shape) - 1))
     genomes = torch.randn((pop, G), generator=torch.Generator(device=dev).manual_seed(seed), dtype=torch.float64,
                           device=dev).mul_(sigma)
     hall = torch.randn((max(pop // 4, 1), G), generator=torch.Generator(device=dev).manual_seed(seed + 1),
@@ -38,12 +39,12 @@ def workload(pop, dev, seed=1234, sigma=3.0):
     return genomes, hall
 
 
-def run(name, pop, dev, warmup, launches):
+def run(name, pop, dev, warmup, launches, shape=SHAPE):
     activation = "sigmoid" if name == "service" else "relu"
     kernel = "split" if name == "service" else name
-    ev = Evaluator(SHAPE, device=dev, activation=activation, kernel=kernel,
+    ev = Evaluator(shape, device=dev, activation=activation, kernel=kernel,
                    precision="f64" if name == "general" else "certified")
-    genomes, hall = workload(pop, dev)
+    genomes, hall = workload(pop, dev, shape=shape)
     sched = ev.selfplay_schedule(pop, hall.shape[0])
     res = None
     for _ in range(warmup):
@@ -62,8 +63,9 @@ def run(name, pop, dev, warmup, launches):
     med = float(np.median(ms))
     q1, q3 = np.percentile(ms, [25, 75])
     frames = int(res.frames.sum())
-    return {"kernel": {"relu": "k_relu", "general": "k_general", "service": "k_service"}[name], "activation": activation,
-            "shape": SHAPE, "pop": pop, "games": 6, "hall": int(hall.shape[0]), "launches": launches, "warmup": warmup,
+    return {"kernel": {"relu": "k_relu", "relu2": "k_relu2", "general": "k_general", "service": "k_service"}[name],
+            "activation": activation, "shape": list(shape), "pop": pop, "games": 6, "hall": int(hall.shape[0]),
+            "launches": launches, "warmup": warmup,
             "ms_median": round(med, 4), "ms_min": round(float(ms.min()), 4), "ms_max": round(float(ms.max()), 4),
             "ms_iqr": round(float(q3 - q1), 4), "stepped_env_steps": int(c[0]), "episode_frames": frames,
             "stepped_env_steps_per_s": round(int(c[0]) / (med * 1e-3), 1), "forwards": int(c[1]),
@@ -73,7 +75,9 @@ def run(name, pop, dev, warmup, launches):
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, general, service")
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, general, service")
+    p.add_argument("--shape", nargs="+", type=int, default=SHAPE,
+                   help="NETWORK_SHAPE (default 6 64 3; relu2 needs two hidden layers, e.g. 6 64 64 3)")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--launches", type=int, default=20)
     args = p.parse_args()
@@ -82,9 +86,9 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     for spec in args.runs:
         name, pop = spec.split(":")
-        if name not in ("relu", "general", "service"):
+        if name not in ("relu", "relu2", "general", "service"):
             p.error(f"unknown kernel {name!r}")
-        print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches)), flush=True)
+        print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches, args.shape)), flush=True)
 
 
 if __name__ == "__main__":
