@@ -30,6 +30,7 @@
  * pg_relu_decide                 the same, as k_relu decides it (ReLU networks: numpy_nn.py:6-9,
  *                                the "alternative activation function" of numpy_nn.py:26)
  * pg_relu2_decide                the same, as k_relu2 decides it (ReLU networks with two hidden layers)
+ * pg_relu_wide_decide            the same, as k_wide's ReLU instances decide it (wide ReLU networks)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
  *                                (the build's SoA Pong; the emulator is absent)
  * pg_ga_select_tournament        tools.selTournament (ga.py:94; DEAP)
@@ -109,7 +110,8 @@ typedef enum pg_precision {
 
 typedef enum pg_kernel {
   PG_KERNEL_AUTO = 0,      /* SPLIT when the shape and precision allow, else GENERAL (ReLU nets: RELU or RELU2
-                              in their scopes, else GENERAL) */
+                              in their scopes; every ReLU net outside them runs on GENERAL under AUTO --
+                              RELU_WIDE is never picked by AUTO, it is chosen explicitly) */
   PG_KERNEL_GENERAL = 1,   /* one wave per game, f64, any NETWORK_SHAPE */
   PG_KERNEL_RESIDENT = 2,  /* retired (round 4): PG_ERR_UNSUPPORTED */
   PG_KERNEL_SPLIT = 3      /* [6, H<=256, 2..4]: half a lane group per paddle's network; f32 forwards with
@@ -130,7 +132,13 @@ typedef enum pg_kernel {
                               layers' f32 weights resident for the game, layer 1's activations all-gathered
                               through LDS each frame.  PG_ERR_UNSUPPORTED for a sigmoid net, any
                               other shape, PG_PREC_F64, horizon > 0 and hard_log.  AUTO picks it for exactly
-                              that scope; every other ReLU configuration runs on GENERAL */
+                              that scope; every other ReLU configuration runs on GENERAL */,
+  PG_KERNEL_RELU_WIDE = 8  /* PG_ACT_RELU only: [6, 2<=H1<=512, 2<=H2<=512, 2..4], with or without bias, f32 or
+                              f64 genomes, PG_PREC_CERTIFIED and PG_PREC_F64 alike, n_games 1..64, whole
+                              episodes: PG_KERNEL_WIDE's kernel, layout and workspace with max(0, z) as the
+                              activation of all three layers -- numpy's f64 values bit for bit, no certificate
+                              (DESIGN 4.2e).  PG_ERR_UNSUPPORTED for a sigmoid net, any other shape, horizon > 0
+                              and hard_log.  Chosen explicitly only: AUTO never picks it */
 } pg_kernel;
 
 /* pg_eval_args.prep: the SPLIT kernel's lane records (one per network of the
@@ -152,7 +160,7 @@ typedef struct pg_net {
   int32_t bias;                  /* 1 = BIAS, weight rows are (in + 1) wide */
   int32_t dtype;                 /* pg_dtype of genomes and opponents */
   int32_t activation;            /* ABI 13: pg_activation; 0 (a zero-initialised net) = the sigmoid.  ReLU
-                                    networks run on PG_KERNEL_RELU / PG_KERNEL_RELU2 / PG_KERNEL_GENERAL and pg_forward (always
+                                    networks run on PG_KERNEL_RELU / PG_KERNEL_RELU2 / PG_KERNEL_RELU_WIDE / PG_KERNEL_GENERAL and pg_forward (always
                                     f64) only: pg_decide, pg_wide_decide, PG_KERNEL_SPLIT, PG_KERNEL_WIDE,
                                     horizon > 0 and hard_log return PG_ERR_UNSUPPORTED for them */
 } pg_net;
@@ -528,6 +536,11 @@ int32_t pg_forward(const pg_forward_args *args, void *stream);
 int32_t pg_decide(const pg_decide_args *args, void *stream);
 size_t pg_wide_decide_workspace_bytes(const pg_wide_decide_args *args);
 int32_t pg_wide_decide(const pg_wide_decide_args *args, void *stream);
+/* The same frame on k_wide's ReLU instances (PG_KERNEL_RELU_WIDE): PG_ACT_RELU networks
+ * [6, 2..512, 2..512, 2..4]; index and the optional f64 act as pg_wide_decide's.
+ * PG_ERR_UNSUPPORTED for a sigmoid net (pg_wide_decide is the sigmoid's). */
+size_t pg_relu_wide_decide_workspace_bytes(const pg_wide_decide_args *args);
+int32_t pg_relu_wide_decide(const pg_wide_decide_args *args, void *stream);
 int32_t pg_relu_decide(const pg_relu_decide_args *args, void *stream);
 /* The same for k_relu2 (PG_KERNEL_RELU2): [6, 2..64, 2..64, 2..4] ReLU networks with bias; z32 is
  * [n, nodes[3]].  The decision code of a k_relu2 frame on given inputs. */

@@ -69,6 +69,12 @@ PRECISION = "certified"
 # "alternative activation function"), applied to every layer.  The drop-in
 # numpy_nn.activation_function starts from it.
 ACTIVATION = "sigmoid"
+# The evaluation kernel (pong_amd.device.KERNELS): "auto" picks by shape,
+# activation and precision.  "relu_wide" is the opt-in for wide ReLU networks
+# (ACTIVATION = "relu", NETWORK_SHAPE [6, 2..512, 2..512, 2..4]), which "auto"
+# leaves on the general kernel; a kernel that cannot run the configured network
+# is an error, never a fallback.
+KERNEL = "auto"
 # Storage type of genomes on the device; float64 keeps Python floats exact.
 GENOME_DTYPE = "float64"
 # "cuda" = the process's current HIP device (one process per GPU).

@@ -59,7 +59,7 @@ struct EvalParams {
   const int32_t *wide_probe_k;
   int32_t *wide_probe_index;  // out [n_genomes] np.argmax
   double *wide_probe_act;     // optional out [n_genomes, nodes[3]]
-  int activation;             // pg_net.activation (k_general, k_relu, k_relu2)
+  int activation;             // pg_net.activation (k_general, k_relu, k_relu2; launch_wide picks k_wide's instance by it)
 };
 
 // Genome blocks / games this launch plays (pg_eval_args.n_active).  Made
@@ -147,7 +147,8 @@ struct DecideParams {
 int32_t launch_decide(const DecideParams &p, int L, int O, bool f64, size_t lds, hipStream_t s);
 
 // [6, H1, H2, O] networks (two hidden layers, H1, H2 <= 512, O in 2..4,
-// n_games <= 8) on the weight-streaming kernel k_wide (pg_wide.hip).
+// n_games <= 8) on the weight-streaming kernel k_wide (pg_wide.hip); launch_wide
+// runs the sigmoid or the ReLU instance (PG_KERNEL_RELU_WIDE) by p.activation.
 bool wide_shape_ok(const pg_net &n, int n_games);
 size_t wide_workspace_bytes(const pg_eval_args *a);
 int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s);

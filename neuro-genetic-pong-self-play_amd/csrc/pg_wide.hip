@@ -26,6 +26,9 @@
 // W . [h; 1] through OpenBLAS dgemv_t, pg_device.hpp blas_dot) with the same
 // sigmoid as k_general, so k_wide and k_general agree bit for bit; the
 // streamed weights are exact (f32 or f64 genomes, widened to f64).
+// The activation is a template parameter (ACT, a pg_activation): the ReLU
+// instances (PG_KERNEL_RELU_WIDE) differ from the sigmoid ones in wide_act /
+// wide_act_out alone.
 #include <hip/hip_runtime.h>
 
 #include "pg_eval.hpp"
@@ -218,6 +221,23 @@ __device__ void wide_prep(unsigned char *scratch, const WideLayout lay, const WT
 // unrolled column keeps the layer loops' register pressure low
 __device__ __noinline__ double sigmoid_f64_call(double z) { return sigmoid_f64(z); }
 
+// The activation of all three layers, a compile-time choice (k_wide's ACT, a
+// pg_activation): the sigmoid as before, or k_general's ReLU expression
+// (pong_ga.hip forward_f64_wave) -- np.maximum(0.0, z): NaN passes through,
+// -0 becomes +0.  No transcendental, so the ReLU instances' values are
+// numpy's bit for bit.  wide_act: inlined (layers 1 and 2); wide_act_out: the
+// output layer's (the sigmoid's out-of-line copy).
+template <int ACT>
+__device__ __forceinline__ double wide_act(double z) {
+  if constexpr (ACT == PG_ACT_RELU) return !(z <= 0.0) ? z : 0.0;
+  else return sigmoid_f64(z);
+}
+template <int ACT>
+__device__ __forceinline__ double wide_act_out(double z) {
+  if constexpr (ACT == PG_ACT_RELU) return !(z <= 0.0) ? z : 0.0;
+  else return sigmoid_f64_call(z);
+}
+
 // index of the q-th set bit of m (q < popcount(m))
 __device__ __forceinline__ int nth_set_bit(unsigned m, int q) {
   for (int i = 0; i < q; ++i) m &= m - 1;
@@ -270,7 +290,7 @@ __device__ __forceinline__ void log_wide(uint32_t *hard_log, uint64_t *counters,
   } while (0)
 #endif
 
-template <int NG, typename WT>
+template <int NG, typename WT, int ACT>
 __global__ __launch_bounds__(kWideThreads) void k_wide(EvalParams p) {
 #ifdef PG_WIDE_STAMPS
   uint64_t stamp_acc[5] = {0, 0, 0, 0, 0}, stamp_last = __builtin_amdgcn_s_memtime();
@@ -517,7 +537,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(EvalParams p) {
             h1[j * NC + c] = blas_dot6(w, feat + c * 8, b, 2);  // (H1 >= 2: wide_shape_ok)
           }
 #pragma unroll 4
-          for (int c = 0; c < NC; ++c) h1[j * NC + c] = sigmoid_f64(h1[j * NC + c]);
+          for (int c = 0; c < NC; ++c) h1[j * NC + c] = wide_act<ACT>(h1[j * NC + c]);
         }
         if (b && t < NC) h1[H1 * NC + t] = 1.0;
         __syncthreads();
@@ -687,7 +707,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(EvalParams p) {
         if (t < H2) {
 #pragma unroll 4
           for (int c = 0; c < NC; ++c) {
-            const double v = sigmoid_f64(h2[t * NC + c]);
+            const double v = wide_act<ACT>(h2[t * NC + c]);
             h2[t * NC + c] = ((mask >> c) & 1) ? v : 0.0;
           }
         }
@@ -728,7 +748,7 @@ __global__ __launch_bounds__(kWideThreads) void k_wide(EvalParams p) {
               const double y = m2o ? __dadd_rn(0.0, blk) : 0.0;
               const double zz =
                   blas_tail([&](int i) { return (double)v[i]; }, [&](int i) { return hp[i * NC]; }, m2o, m3o, y);
-              outv[c * 4 + o] = sigmoid_f64_call(zz);
+              outv[c * 4 + o] = wide_act_out<ACT>(zz);
             }
           };
           if (w3r) {
@@ -884,7 +904,7 @@ size_t wide_workspace_bytes(const pg_eval_args *a) {
   return (size_t)wide_grid(wide_items(a->n_genomes, a->n_games, NG)) * (size_t)(NG + 1) * (size_t)l.net_bytes;
 }
 
-template <int NG, typename WT>
+template <int NG, typename WT, int ACT>
 static int32_t launch_wide_t(EvalParams p, void *scratch, hipStream_t s) {
   int lds = wide_lds_bytes(2 * NG, p.nodes[1], p.nodes[2], p.bias);
   if (lds > 160 * 1024) return fail(PG_ERR_UNSUPPORTED, "k_wide needs %d bytes of LDS", lds);
@@ -893,18 +913,23 @@ static int32_t launch_wide_t(EvalParams p, void *scratch, hipStream_t s) {
   p.wide_w3_resident = lds + w3_bytes <= 160 * 1024 ? 1 : 0;
   if (p.wide_w3_resident) lds += w3_bytes;
   // above 64 KB of dynamic LDS; an older runtime that rejects the attribute launches anyway
-  (void)hipFuncSetAttribute((const void *)k_wide<NG, WT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  (void)hipFuncSetAttribute((const void *)k_wide<NG, WT, ACT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   (void)hipGetLastError();
   const int grid = wide_grid(wide_items(p.n_genomes, p.n_games, NG));  // wide_workspace_bytes sized the scratch for it
   if (grid <= 0) return PG_OK;
   p.wide_scratch = scratch;
-  hipLaunchKernelGGL((k_wide<NG, WT>), dim3(grid), dim3(kWideThreads), (size_t)lds, s, p);
+  hipLaunchKernelGGL((k_wide<NG, WT, ACT>), dim3(grid), dim3(kWideThreads), (size_t)lds, s, p);
   PG_HIP(hipGetLastError());
   return PG_OK;
 }
 
 int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s) {
-  return dtype == PG_F64 ? launch_wide_t<4, double>(p, scratch, s) : launch_wide_t<6, float>(p, scratch, s);
+  // the activation picks the instance (p.activation is not read in the kernel); NG per dtype as wide_ng
+  if (p.activation == PG_ACT_RELU)
+    return dtype == PG_F64 ? launch_wide_t<4, double, PG_ACT_RELU>(p, scratch, s)
+                           : launch_wide_t<6, float, PG_ACT_RELU>(p, scratch, s);
+  return dtype == PG_F64 ? launch_wide_t<4, double, PG_ACT_SIGMOID>(p, scratch, s)
+                         : launch_wide_t<6, float, PG_ACT_SIGMOID>(p, scratch, s);
 }
 
 }  // namespace pg

@@ -761,7 +761,8 @@ size_t pg_eval_workspace_bytes(const pg_eval_args *a) {
   if (!a) return n;
   const int kernel = resolve_kernel(a);
   if (kernel == PG_KERNEL_SPLIT) n += split_records_bytes(a);
-  if (kernel == PG_KERNEL_WIDE && wide_shape_ok(a->net, a->n_games)) n += (wide_workspace_bytes(a) + 255) / 256 * 256;
+  if ((kernel == PG_KERNEL_WIDE || kernel == PG_KERNEL_RELU_WIDE) && wide_shape_ok(a->net, a->n_games))
+    n += (wide_workspace_bytes(a) + 255) / 256 * 256;
   return n;
 }
 
@@ -791,6 +792,12 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
       return fail(PG_ERR_UNSUPPORTED, "relu2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4] with bias");
     if (a->precision == PG_PREC_F64) return fail(PG_ERR_UNSUPPORTED, "relu2 kernel is the certified-precision path");
   }
+  if (a->kernel == PG_KERNEL_RELU_WIDE) {  // the same; exact f64 under either precision
+    if (a->net.activation != PG_ACT_RELU)
+      return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu_wide kernel evaluates PG_ACT_RELU networks only (use WIDE)");
+    if (!wide_shape_ok(a->net, a->n_games))
+      return fail(PG_ERR_UNSUPPORTED, "relu_wide kernel needs NETWORK_SHAPE [6, 2..512, 2..512, 2..4]");
+  }
   if (a->n_genomes == 0) {  // nothing to play (e.g. an empty shard); the counters still read zero
     if (a->counters) PG_HIP(hipMemsetAsync(a->counters, 0, 16 * sizeof(uint64_t), (hipStream_t)stream));
     return PG_OK;
@@ -810,9 +817,9 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   if (a->trace && (a->trace_games < 0 || a->trace_cap < 1))
     return fail(PG_ERR_INVALID, "trace needs trace_games >= 0 and trace_cap >= 1");
   if (a->prep < PG_PREP_ALL || a->prep > PG_PREP_REST) return fail(PG_ERR_INVALID, "prep=%d", a->prep);
-  if (a->net.activation == PG_ACT_RELU) {  // ReLU networks: k_relu, k_relu2 or k_general, whole episodes, no hard-case log
+  if (a->net.activation == PG_ACT_RELU) {  // ReLU networks: k_relu, k_relu2, k_wide's ReLU instances or k_general, whole episodes, no hard-case log
     if (a->kernel == PG_KERNEL_SPLIT || a->kernel == PG_KERNEL_WIDE)
-      return fail(PG_ERR_UNSUPPORTED, "activation relu: the %s kernel evaluates sigmoid networks only (use RELU, RELU2 or GENERAL)",
+      return fail(PG_ERR_UNSUPPORTED, "activation relu: the %s kernel evaluates sigmoid networks only (use RELU, RELU2, RELU_WIDE or GENERAL)",
                   a->kernel == PG_KERNEL_SPLIT ? "split" : "wide");
     if (a->horizon > 0) return fail(PG_ERR_UNSUPPORTED, "activation relu: no fixed-horizon mode (horizon must be 0)");
     if (a->hard_log) return fail(PG_ERR_UNSUPPORTED, "activation relu: no hard-case log (hard_log must be NULL)");
@@ -875,7 +882,10 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   }  // the split kernel's k_prep_records zeroes the work header and the counters itself
   const bool res_ok = resident_shape_ok(a->net);
   const bool wide_ok = wide_shape_ok(a->net, a->n_games);
-  if (kernel == PG_KERNEL_WIDE) {
+  if (kernel == PG_KERNEL_RELU_WIDE) {  // (activation and shape were checked on entry): k_wide's ReLU instances
+    rc = launch_wide(p, a->net.dtype, (char *)a->workspace + eval_base_workspace(a), s);
+    if (rc != PG_OK) return rc;
+  } else if (kernel == PG_KERNEL_WIDE) {
     if (!wide_ok)
       return fail(PG_ERR_UNSUPPORTED, "wide kernel needs NETWORK_SHAPE [6, H1<=512, H2<=512, 1..4] and n_games <= 8");
     rc = launch_wide(p, a->net.dtype, (char *)a->workspace + eval_base_workspace(a), s);
@@ -1019,14 +1029,10 @@ size_t pg_wide_decide_workspace_bytes(const pg_wide_decide_args *a) {
   return 256 + (wide_workspace_bytes(&e) + 255) / 256 * 256;
 }
 
-int32_t pg_wide_decide(const pg_wide_decide_args *a, void *stream) {
-  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
-  int32_t rc = check_net(a->net, false);
-  if (rc != PG_OK) return rc;
-  if (a->net.activation != PG_ACT_SIGMOID)
-    return fail(PG_ERR_UNSUPPORTED, "pg_wide_decide: activation relu -- the wide kernel evaluates sigmoid networks only");
+// one frame of k_wide (the instance of a->net.activation) per pass; name: the entry point, for its messages
+static int32_t wide_decide_run(const char *name, const pg_wide_decide_args *a, void *stream) {
   if (!wide_shape_ok(a->net, 1))
-    return fail(PG_ERR_UNSUPPORTED, "pg_wide_decide: the wide kernel's shapes [6, H1<=512, H2<=512, 1..4] only");
+    return fail(PG_ERR_UNSUPPORTED, "%s: the wide kernel's shapes [6, H1<=512, H2<=512, 1..4] only", name);
   if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);
   if (a->n == 0) return PG_OK;
   const int G = gene_count(a->net);
@@ -1051,11 +1057,33 @@ int32_t pg_wide_decide(const pg_wide_decide_args *a, void *stream) {
   p.n_nodes = a->net.n_nodes;
   p.bias = a->net.bias ? 1 : 0;
   p.max_width = max_width(a->net);
+  p.activation = a->net.activation;
   p.wide_probe_k = a->k;
   p.wide_probe_index = a->index;
   p.wide_probe_act = a->act;
   PG_HIP(hipMemsetAsync(a->workspace, 0, 256, s));
   return launch_wide(p, a->net.dtype, (char *)a->workspace + 256, s);
+}
+
+int32_t pg_wide_decide(const pg_wide_decide_args *a, void *stream) {
+  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
+  int32_t rc = check_net(a->net, false);
+  if (rc != PG_OK) return rc;
+  if (a->net.activation != PG_ACT_SIGMOID)
+    return fail(PG_ERR_UNSUPPORTED, "pg_wide_decide: activation relu -- the wide kernel evaluates sigmoid networks only");
+  return wide_decide_run("pg_wide_decide", a, stream);
+}
+
+// The same frame on k_wide's ReLU instances (PG_KERNEL_RELU_WIDE); the workspace is pg_wide_decide's.
+size_t pg_relu_wide_decide_workspace_bytes(const pg_wide_decide_args *a) { return pg_wide_decide_workspace_bytes(a); }
+
+int32_t pg_relu_wide_decide(const pg_wide_decide_args *a, void *stream) {
+  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
+  int32_t rc = check_net(a->net, false);
+  if (rc != PG_OK) return rc;
+  if (a->net.activation != PG_ACT_RELU)
+    return fail(PG_ERR_UNSUPPORTED, "pg_relu_wide_decide: activation sigmoid -- PG_ACT_RELU networks only (pg_wide_decide)");
+  return wide_decide_run("pg_relu_wide_decide", a, stream);
 }
 
 int32_t pg_physics_reset(int32_t *state, int32_t n, const uint64_t *seeds, const int32_t *one_player,

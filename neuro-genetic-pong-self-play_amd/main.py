@@ -22,6 +22,7 @@ try:
 except ImportError:
     from pong_amd.deap_compat import algorithms, tools
 
+import config
 import ga
 import numpy_nn
 import utils
@@ -36,7 +37,8 @@ def _evaluator():
     # the network shape is utils' binding, as create_model_from_genes sees it (utils.py:80-87)
     return runtime.evaluator(utils.NETWORK_SHAPE, utils.BIAS, GAMES_TO_PLAY, GENOME_DTYPE,  # noqa: F405
                              PRECISION, PHYSICS_SEED, DEVICE, TIMEOUT_THRESH, WIN_SCORE,  # noqa: F405
-                             activation=numpy_nn.activation())  # numpy_nn.py:26, as bound at this call
+                             activation=numpy_nn.activation(),  # numpy_nn.py:26, as bound at this call
+                             kernel=config.KERNEL)  # config.py's knob, as set at this call
 
 
 def _fitness_tuples(fitness, status):
@@ -205,7 +207,7 @@ def perform_episode(env, left_model, right_model, render=False, score_multiplier
         return perform_episode_stepwise(env, left_model, right_model, render, score_multiplier)
     ev = runtime.evaluator(right_model.nodes, bool(right_model.bias), 1, "float64", PRECISION,  # noqa: F405
                            _slot_seed(getattr(env, "game", 0)), DEVICE, TIMEOUT_THRESH, WIN_SCORE,  # noqa: F405
-                           activation=numpy_nn.activation())
+                           activation=numpy_nn.activation(), kernel=config.KERNEL)
     dev = ev.device
     kind_t = torch.tensor([[kind]], dtype=torch.int32, device=dev)
     opp_t = torch.zeros((1, 1), dtype=torch.int32, device=dev)

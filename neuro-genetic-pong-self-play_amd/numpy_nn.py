@@ -72,7 +72,8 @@ class NeuralNetwork:
 
     def _evaluator(self):
         return runtime.evaluator(self.nodes, bool(self.bias), genome_dtype="float64",
-                                 precision=config.PRECISION, device=config.DEVICE, activation=activation())
+                                 precision=config.PRECISION, device=config.DEVICE, activation=activation(),
+                                 kernel=config.KERNEL)
 
     def populate_weights(self, weights):
         """Slice the flat genome into per-layer (out, in + bias) matrices."""

@@ -29,6 +29,7 @@ PG_SCHED_REFERENCE, PG_SCHED_SELFPLAY = 0, 1
 PG_KERNEL_AUTO, PG_KERNEL_GENERAL, PG_KERNEL_RESIDENT, PG_KERNEL_SPLIT, PG_KERNEL_WIDE, PG_KERNEL_STAGED = 0, 1, 2, 3, 4, 5
 PG_KERNEL_RELU = 6
 PG_KERNEL_RELU2 = 7
+PG_KERNEL_RELU_WIDE = 8
 PG_STATE_FIELDS = 16
 STATE_FIELD_NAMES = ("ball_x", "ball_y", "ball_vx", "ball_vy", "ball_visible", "serve_timer",
                      "serve_dir", "hits", "point", "lpy", "rpy", "score1", "score2",
@@ -208,6 +209,8 @@ SIGNATURES = {
     "pg_decide": (ctypes.c_int32, [ctypes.POINTER(PgDecideArgs), _vp]),
     "pg_wide_decide_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PgWideDecideArgs)]),
     "pg_wide_decide": (ctypes.c_int32, [ctypes.POINTER(PgWideDecideArgs), _vp]),
+    "pg_relu_wide_decide_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PgWideDecideArgs)]),
+    "pg_relu_wide_decide": (ctypes.c_int32, [ctypes.POINTER(PgWideDecideArgs), _vp]),
     "pg_relu_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_relu2_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_physics_reset": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp, _vp]),

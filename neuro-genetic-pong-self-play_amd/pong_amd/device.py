@@ -17,7 +17,8 @@ from . import _lib as L
 PRECISIONS = {"certified": L.PG_PREC_CERTIFIED, "f64": L.PG_PREC_F64}
 PREPS = {"all": L.PG_PREP_ALL, "genomes": L.PG_PREP_GENOMES, "rest": L.PG_PREP_REST}
 KERNELS = {"auto": L.PG_KERNEL_AUTO, "general": L.PG_KERNEL_GENERAL, "split": L.PG_KERNEL_SPLIT,
-           "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU, "relu2": L.PG_KERNEL_RELU2}
+           "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU, "relu2": L.PG_KERNEL_RELU2,
+           "relu_wide": L.PG_KERNEL_RELU_WIDE}
 ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
@@ -362,12 +363,27 @@ class Evaluator:
         """k_wide's own decision (pg_wide_decide: one frame of the evaluation
         kernel per pass) on doubled-centroid features k [n, 6] int32: returns
         (argmax index [n] int32, output activations [n, out] f64)."""
+        return self._wide_decide("pg_wide_decide", genomes, k, genome_index)
+
+    def relu_wide_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The same on k_wide's ReLU instances (pg_relu_wide_decide: one frame of
+        kernel="relu_wide", ReLU networks [6, 2..512, 2..512, 2..4])."""
+        return self._wide_decide("pg_relu_wide_decide", genomes, k, genome_index)
+
+    def _wide_decide(self, entry: str, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor]):
         dev = self.device
         _need(genomes, "genomes", self.dtype, dev)
+        if genomes.dim() != 2 or genomes.shape[1] < self.genes:
+            raise ValueError(f"genomes must be [n, >= {self.genes}], got {tuple(genomes.shape)}")
         n = k.shape[0]
         _need(k, "k", torch.int32, dev, (n, 6))
         if genome_index is not None:
             _need(genome_index, "genome_index", torch.int32, dev, (n,))
+            # one host sync: an out-of-range row would fault the GPU
+            if n and bool(((genome_index < 0) | (genome_index >= genomes.shape[0])).any()):
+                raise ValueError(f"genome_index must index the {genomes.shape[0]}-row genomes tensor")
+        elif n > genomes.shape[0]:
+            raise ValueError("more passes than genome rows (pass genome_index)")
         index = torch.empty(n, dtype=torch.int32, device=dev)
         act = torch.empty((n, self.nodes[-1]), dtype=torch.float64, device=dev)
         a = L.PgWideDecideArgs()
@@ -379,11 +395,11 @@ class Evaluator:
         a.k = _ptr(k)
         a.index = _ptr(index)
         a.act = _ptr(act)
-        nbytes = L.lib().pg_wide_decide_workspace_bytes(ctypes.byref(a))
+        nbytes = getattr(L.lib(), entry + "_workspace_bytes")(ctypes.byref(a))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         a.workspace, a.workspace_bytes = _ptr(ws), nbytes
         with torch.cuda.device(dev):
-            L.check("pg_wide_decide", L.lib().pg_wide_decide(ctypes.byref(a), _stream(dev)))
+            L.check(entry, getattr(L.lib(), entry)(ctypes.byref(a), _stream(dev)))
         return index, act
 
 

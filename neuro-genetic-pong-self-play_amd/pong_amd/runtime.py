@@ -1,4 +1,4 @@
-"""Per-process device state: one Evaluator per (shape, bias, dtype, precision, activation),
+"""Per-process device state: one Evaluator per (shape, bias, dtype, precision, activation, kernel),
 created on first use on the configured device (config.DEVICE)."""
 from __future__ import annotations
 
@@ -18,9 +18,9 @@ def _torch_dtype(name: str):
 
 
 def evaluator(nodes, bias=True, n_games=6, genome_dtype="float64", precision="certified",
-              seed=0, device="cuda", timeout_thresh=0, win_score=0, activation="sigmoid") -> D.Evaluator:
+              seed=0, device="cuda", timeout_thresh=0, win_score=0, activation="sigmoid", kernel="auto") -> D.Evaluator:
     key = (tuple(int(n) for n in nodes), bool(bias), int(n_games), genome_dtype, precision, int(seed), str(device),
-           int(timeout_thresh), int(win_score), str(activation))
+           int(timeout_thresh), int(win_score), str(activation), str(kernel))
     with _lock:
         ev = _evaluators.get(key)
         if ev is None:
@@ -29,7 +29,7 @@ def evaluator(nodes, bias=True, n_games=6, genome_dtype="float64", precision="ce
                 dev = torch.device("cuda", torch.cuda.current_device())
             ev = D.Evaluator(list(nodes), bias=bias, dtype=_torch_dtype(genome_dtype), device=dev,
                              n_games=n_games, precision=precision, seed=seed,
-                             timeout_thresh=timeout_thresh, win_score=win_score, activation=activation)
+                             timeout_thresh=timeout_thresh, win_score=win_score, activation=activation, kernel=kernel)
             _evaluators[key] = ev
         return ev
 

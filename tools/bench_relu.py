@@ -12,6 +12,13 @@ interquartile range) of >= 20 launches are reported.
     python tools/bench_relu.py                      # the four runs
     python tools/bench_relu.py --runs relu:4096 general:4096 --launches 30
     python tools/bench_relu.py --shape 6 64 64 3 --runs relu2:4096 general:4096   # k_relu2
+    python tools/bench_relu.py --shape 6 512 512 3 --dtype float32 --launches 5 \
+        --runs relu_wide:4096 general:4096                                        # k_wide's ReLU instances (4.2e)
+
+relu_wide runs also report the network passes (counter [7]) and the streaming
+rate passes x gene bytes / launch time, as bench.py --config wide does for the
+sigmoid k_wide.  --dtype is the genome storage type (default float64, the 4.2c
+workload; float32 draws the same N(0, 3) genes in f32, BASELINE config 5's storage).
 """
 import argparse
 import json
@@ -30,21 +37,25 @@ SHAPE = [6, 64, 3]
 RUNS = ["relu:4096", "general:4096", "relu:65536", "service:65536"]
 
 
-def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE):
+def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64):
     G = sum((shape[i] + 1) * shape[i + 1] for i in range(len(shape) - 1))
-    genomes = torch.randn((pop, G), generator=torch.Generator(device=dev).manual_seed(seed), dtype=torch.float64,
+    genomes = torch.randn((pop, G), generator=torch.Generator(device=dev).manual_seed(seed), dtype=dtype,
                           device=dev).mul_(sigma)
     hall = torch.randn((max(pop // 4, 1), G), generator=torch.Generator(device=dev).manual_seed(seed + 1),
-                       dtype=torch.float64, device=dev).mul_(sigma)
+                       dtype=dtype, device=dev).mul_(sigma)
     return genomes, hall
 
 
-def run(name, pop, dev, warmup, launches, shape=SHAPE):
+KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu_wide": "k_wide<relu>", "general": "k_general",
+                "service": "k_service"}
+
+
+def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64):
     activation = "sigmoid" if name == "service" else "relu"
     kernel = "split" if name == "service" else name
-    ev = Evaluator(shape, device=dev, activation=activation, kernel=kernel,
+    ev = Evaluator(shape, device=dev, dtype=dtype, activation=activation, kernel=kernel,
                    precision="f64" if name == "general" else "certified")
-    genomes, hall = workload(pop, dev, shape=shape)
+    genomes, hall = workload(pop, dev, shape=shape, dtype=dtype)
     sched = ev.selfplay_schedule(pop, hall.shape[0])
     res = None
     for _ in range(warmup):
@@ -63,7 +74,7 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE):
     med = float(np.median(ms))
     q1, q3 = np.percentile(ms, [25, 75])
     frames = int(res.frames.sum())
-    return {"kernel": {"relu": "k_relu", "relu2": "k_relu2", "general": "k_general", "service": "k_service"}[name],
+    out = {"kernel": KERNEL_NAMES[name], "genome_dtype": str(dtype).replace("torch.", ""),
             "activation": activation, "shape": list(shape), "pop": pop, "games": 6, "hall": int(hall.shape[0]),
             "launches": launches, "warmup": warmup,
             "ms_median": round(med, 4), "ms_min": round(float(ms.min()), 4), "ms_max": round(float(ms.max()), 4),
@@ -71,24 +82,33 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE):
             "stepped_env_steps_per_s": round(int(c[0]) / (med * 1e-3), 1), "forwards": int(c[1]),
             "f64_forwards": int(c[2]), "f64_share": round(int(c[2]) / max(int(c[1]), 1), 6),
             "device": torch.cuda.get_device_name(dev)}
+    if name == "relu_wide":  # each network pass streams one network's genes once
+        gene_bytes = ev.genes * genomes.element_size()
+        out["network_passes"] = int(c[7])
+        out["rally_frames_advanced"] = int(c[8])
+        out["stream_TB_per_s"] = round(int(c[7]) * gene_bytes / (med * 1e-3) / 1e12, 3)
+        out["stream_TB_per_s_min_max"] = [round(int(c[7]) * gene_bytes / (float(t) * 1e-3) / 1e12, 3) for t in (ms.max(), ms.min())]
+    return out
 
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, general, service")
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, general, service")
     p.add_argument("--shape", nargs="+", type=int, default=SHAPE,
                    help="NETWORK_SHAPE (default 6 64 3; relu2 needs two hidden layers, e.g. 6 64 64 3)")
     p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--launches", type=int, default=20)
+    p.add_argument("--launches", type=int, default=20, help="timed launches (>= 20; >= 5 for layers wider than 256)")
+    p.add_argument("--dtype", default="float64", choices=["float64", "float32"], help="genome storage type")
     args = p.parse_args()
-    if args.launches < 20:
-        p.error("--launches must be >= 20")
+    if args.launches < (5 if max(args.shape[1:-1]) > 256 else 20):
+        p.error("--launches must be >= 20 (>= 5 for layers wider than 256: seconds per launch)")
     dev = torch.device("cuda", torch.cuda.current_device())
     for spec in args.runs:
         name, pop = spec.split(":")
-        if name not in ("relu", "relu2", "general", "service"):
+        if name not in KERNEL_NAMES:
             p.error(f"unknown kernel {name!r}")
-        print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches, args.shape)), flush=True)
+        print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches, args.shape,
+                             getattr(torch, args.dtype))), flush=True)
 
 
 if __name__ == "__main__":
