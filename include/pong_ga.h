@@ -31,6 +31,7 @@
  *                                the "alternative activation function" of numpy_nn.py:26)
  * pg_relu2_decide                the same, as k_relu2 decides it (ReLU networks with two hidden layers)
  * pg_relu_wide_decide            the same, as k_wide's ReLU instances decide it (wide ReLU networks)
+ * pg_sig2_decide                 the same, as k_sig2 decides it (sigmoid networks with two hidden layers)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
  *                                (the build's SoA Pong; the emulator is absent)
  * pg_ga_select_tournament        tools.selTournament (ga.py:94; DEAP)
@@ -138,7 +139,16 @@ typedef enum pg_kernel {
                               episodes: PG_KERNEL_WIDE's kernel, layout and workspace with max(0, z) as the
                               activation of all three layers -- numpy's f64 values bit for bit, no certificate
                               (DESIGN 4.2e).  PG_ERR_UNSUPPORTED for a sigmoid net, any other shape, horizon > 0
-                              and hard_log.  Chosen explicitly only: AUTO never picks it */
+                              and hard_log.  Chosen explicitly only: AUTO never picks it */,
+  PG_KERNEL_SIG2 = 9       /* PG_ACT_SIGMOID only: [6, 2<=H1<=64, 2<=H2<=64, 2..4] with bias, certified precision,
+                              f32 or f64 genomes, every opponent kind, whole episodes: k_relu2's layout (all
+                              three layers' f32 weights resident for the game, layer 1 all-gathered through LDS)
+                              with sigmoid_f32 in both hidden layers, a static f32 bound through the two
+                              sigmoid layers and k_service's decision cascade on the output pre-activations,
+                              the rest recomputed in f64 in numpy's order.  Every frame is
+                              stepped (counters [8] = [12] = 0); no lane records, no workspace beyond the
+                              base.  PG_ERR_UNSUPPORTED for a ReLU net, any other shape, no bias, PG_PREC_F64,
+                              horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it */
 } pg_kernel;
 
 /* pg_eval_args.prep: the SPLIT kernel's lane records (one per network of the
@@ -545,6 +555,13 @@ int32_t pg_relu_decide(const pg_relu_decide_args *args, void *stream);
 /* The same for k_relu2 (PG_KERNEL_RELU2): [6, 2..64, 2..64, 2..4] ReLU networks with bias; z32 is
  * [n, nodes[3]].  The decision code of a k_relu2 frame on given inputs. */
 int32_t pg_relu2_decide(const pg_relu_decide_args *args, void *stream);
+/* The decision code of a k_sig2 frame (PG_KERNEL_SIG2) on given inputs: PG_ACT_SIGMOID networks
+ * [6, 2..64, 2..64, 2..4] with bias, the argument struct of pg_relu_decide.  index [n]: the argmax of
+ * numpy's f64 sigmoid outputs; stage [n]: 0 the f32 certificate (certify_c under the network's static
+ * bound), 1 tight_gap_move, 2 plateau_f32, 3 the f64 forward in numpy's order; z32 [n, nodes[3]]: the
+ * f32 output pre-activations; bound [n]: e >= |z32 - numpy's f64 pre-activation| (inf: the network is
+ * always decided in f64).  PG_ERR_UNSUPPORTED for a ReLU net, another shape or a net without bias. */
+int32_t pg_sig2_decide(const pg_relu_decide_args *args, void *stream);
 int32_t pg_physics_reset(int32_t *state, int32_t n, const uint64_t *seeds,
                          const int32_t *one_player, void *stream);
 /* actions [n]: bit0 right up, bit1 right down, bit2 left up, bit3 left down */

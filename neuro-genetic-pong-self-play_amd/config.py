@@ -72,8 +72,11 @@ ACTIVATION = "sigmoid"
 # The evaluation kernel (pong_amd.device.KERNELS): "auto" picks by shape,
 # activation and precision.  "relu_wide" is the opt-in for wide ReLU networks
 # (ACTIVATION = "relu", NETWORK_SHAPE [6, 2..512, 2..512, 2..4]), which "auto"
-# leaves on the general kernel; a kernel that cannot run the configured network
-# is an error, never a fallback.
+# leaves on the general kernel; "sig2" is the opt-in certified f32 kernel for
+# two-hidden-layer sigmoid networks (ACTIVATION = "sigmoid", NETWORK_SHAPE
+# [6, 2..64, 2..64, 2..4], BIAS), which "auto" leaves on the general kernel (on
+# the wide one from 64 units up); a kernel that cannot run the configured
+# network is an error, never a fallback.
 KERNEL = "auto"
 # Storage type of genomes on the device; float64 keeps Python floats exact.
 GENOME_DTYPE = "float64"

@@ -15,6 +15,7 @@
 //                         arithmetic with activations staged in LDS (sigmoid or ReLU).
 //   k_relu<LN,U,O,WT>     [6, H<=256, O] ReLU networks (pg_relu.hip).
 //   k_relu2<LN,U1,U2,O,WT>  [6, H1<=64, H2<=64, O] ReLU networks (pg_relu2.hip).
+//   k_sig2<LN,U1,U2,O,WT>   [6, H1<=64, H2<=64, O] sigmoid networks (pg_sig2.hip).
 //   k_fitness             sum(all_rewards) / GAMES_TO_PLAY in the reference order.
 //   k_forward_*           NeuralNetwork.run batched (parity entry point).
 //   k_physics_*           the SoA Pong stepper on its own.
@@ -798,6 +799,16 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     if (!wide_shape_ok(a->net, a->n_games))
       return fail(PG_ERR_UNSUPPORTED, "relu_wide kernel needs NETWORK_SHAPE [6, 2..512, 2..512, 2..4]");
   }
+  if (a->kernel == PG_KERNEL_SIG2) {  // the same: every refusal of its scope
+    if (a->net.activation != PG_ACT_SIGMOID)
+      return fail(PG_ERR_UNSUPPORTED, "activation relu: the sig2 kernel evaluates sigmoid networks only (use RELU2)");
+    if (!sig2_shape_ok(a->net))
+      return fail(PG_ERR_UNSUPPORTED, "sig2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4]");
+    if (!a->net.bias) return fail(PG_ERR_UNSUPPORTED, "sig2 kernel needs a network with bias");
+    if (a->precision == PG_PREC_F64) return fail(PG_ERR_UNSUPPORTED, "sig2 kernel is the certified-precision path");
+    if (a->horizon > 0) return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no fixed-horizon mode (horizon must be 0)");
+    if (a->hard_log) return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no hard-case log (hard_log must be NULL)");
+  }
   if (a->n_genomes == 0) {  // nothing to play (e.g. an empty shard); the counters still read zero
     if (a->counters) PG_HIP(hipMemsetAsync(a->counters, 0, 16 * sizeof(uint64_t), (hipStream_t)stream));
     return PG_OK;
@@ -818,9 +829,9 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     return fail(PG_ERR_INVALID, "trace needs trace_games >= 0 and trace_cap >= 1");
   if (a->prep < PG_PREP_ALL || a->prep > PG_PREP_REST) return fail(PG_ERR_INVALID, "prep=%d", a->prep);
   if (a->net.activation == PG_ACT_RELU) {  // ReLU networks: k_relu, k_relu2, k_wide's ReLU instances or k_general, whole episodes, no hard-case log
-    if (a->kernel == PG_KERNEL_SPLIT || a->kernel == PG_KERNEL_WIDE)
+    if (a->kernel == PG_KERNEL_SPLIT || a->kernel == PG_KERNEL_WIDE || a->kernel == PG_KERNEL_SIG2)
       return fail(PG_ERR_UNSUPPORTED, "activation relu: the %s kernel evaluates sigmoid networks only (use RELU, RELU2, RELU_WIDE or GENERAL)",
-                  a->kernel == PG_KERNEL_SPLIT ? "split" : "wide");
+                  a->kernel == PG_KERNEL_SPLIT ? "split" : (a->kernel == PG_KERNEL_WIDE ? "wide" : "sig2"));
     if (a->horizon > 0) return fail(PG_ERR_UNSUPPORTED, "activation relu: no fixed-horizon mode (horizon must be 0)");
     if (a->hard_log) return fail(PG_ERR_UNSUPPORTED, "activation relu: no hard-case log (hard_log must be NULL)");
   } else if (a->kernel == PG_KERNEL_RELU) {
@@ -912,6 +923,9 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_RELU2) {  // (activation, shape and precision were checked on entry)
     rc = launch_relu2(p, a->net.dtype, s);
+    if (rc != PG_OK) return rc;
+  } else if (kernel == PG_KERNEL_SIG2) {  // (the same)
+    rc = launch_sig2(p, a->net.dtype, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_GENERAL) {
     const size_t lds = 2 * (size_t)(p.max_width + 1) * sizeof(double);

@@ -30,6 +30,7 @@ PG_KERNEL_AUTO, PG_KERNEL_GENERAL, PG_KERNEL_RESIDENT, PG_KERNEL_SPLIT, PG_KERNE
 PG_KERNEL_RELU = 6
 PG_KERNEL_RELU2 = 7
 PG_KERNEL_RELU_WIDE = 8
+PG_KERNEL_SIG2 = 9
 PG_STATE_FIELDS = 16
 STATE_FIELD_NAMES = ("ball_x", "ball_y", "ball_vx", "ball_vy", "ball_visible", "serve_timer",
                      "serve_dir", "hits", "point", "lpy", "rpy", "score1", "score2",
@@ -213,6 +214,7 @@ SIGNATURES = {
     "pg_relu_wide_decide": (ctypes.c_int32, [ctypes.POINTER(PgWideDecideArgs), _vp]),
     "pg_relu_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_relu2_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
+    "pg_sig2_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_physics_reset": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp, _vp]),
     "pg_physics_step": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp]),
     "pg_ga_select_tournament": (ctypes.c_int32, [ctypes.POINTER(PgSelectArgs), _vp]),

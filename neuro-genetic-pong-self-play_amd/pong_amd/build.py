@@ -11,14 +11,15 @@ from ._lib import LIB_PATH, PKG_DIR, REPO_DIR
 CSRC = os.path.join(PKG_DIR, "csrc")
 HEADERS = [os.path.join(CSRC, h) for h in ("pg_device.hpp", "pg_f64math.h", "pg_eval.hpp", "pg_cascade.hpp",
                                            "pg_service.hpp", "pg_relu.hpp", "pg_relu_bound.h", "pg_relu2.hpp",
-                                           "pg_relu2_bound.h")] + [os.path.join(REPO_DIR, "include", "pong_ga.h")]
+                                           "pg_relu2_bound.h", "pg_sig2.hpp", "pg_sig2_bound.h")] + [os.path.join(REPO_DIR, "include", "pong_ga.h")]
 # one translation unit per kernel family, compiled in parallel and linked into one .so;
 # pg_service_more.hip is compiled once per (lanes per game, genome type): its ~100
 # k_service instantiations took 10 minutes as one unit
 # (object name, source, extra flags)
 UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_wide", "pg_wide.hip", []), ("pg_pixels", "pg_pixels.hip", []),
          ("pg_hof", "pg_hof.hip", []), ("pg_gen", "pg_gen.hip", []), ("pg_decide", "pg_decide.hip", []),
-         ("pg_relu", "pg_relu.hip", []), ("pg_relu2", "pg_relu2.hip", [])] + [
+         ("pg_relu", "pg_relu.hip", []), ("pg_relu2", "pg_relu2.hip", []),
+         ("pg_sig2", "pg_sig2.hip", [])] + [
     (f"pg_service_more_L{L}_{f}", "pg_service_more.hip",
      [f"-DPG_MORE_L={L}", f"-DPG_MORE_F64={f}"] + (["-DPG_MORE_DISPATCH"] if (L, f) == (8, 1) else []))
     for L in (8, 16, 32, 64) for f in (1, 0)]

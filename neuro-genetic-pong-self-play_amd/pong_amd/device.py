@@ -18,7 +18,7 @@ PRECISIONS = {"certified": L.PG_PREC_CERTIFIED, "f64": L.PG_PREC_F64}
 PREPS = {"all": L.PG_PREP_ALL, "genomes": L.PG_PREP_GENOMES, "rest": L.PG_PREP_REST}
 KERNELS = {"auto": L.PG_KERNEL_AUTO, "general": L.PG_KERNEL_GENERAL, "split": L.PG_KERNEL_SPLIT,
            "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU, "relu2": L.PG_KERNEL_RELU2,
-           "relu_wide": L.PG_KERNEL_RELU_WIDE}
+           "relu_wide": L.PG_KERNEL_RELU_WIDE, "sig2": L.PG_KERNEL_SIG2}
 ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
@@ -328,6 +328,16 @@ class Evaluator:
         """The same for the two-hidden-layer ReLU kernel (pg_relu2_decide:
         k_relu2's decision code, [6, 2..64, 2..64, 2..4] networks with bias)."""
         return self._relu_decide("pg_relu2_decide", genomes, k, genome_index)
+
+    def sig2_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The two-hidden-layer sigmoid kernel's own decision (pg_sig2_decide:
+        k_sig2's decision code, [6, 2..64, 2..64, 2..4] sigmoid networks with
+        bias) on doubled-centroid features k [n, 6] int32: returns (argmax index
+        [n] int32, stage [n] int32: 0 the f32 certificate, 1 tight_gap_move,
+        2 plateau_f32, 3 recomputed in f64, z32 [n, out] f32 output
+        pre-activations, bound [n] f32 on |z32 - numpy's f64 pre-activation|;
+        inf = the network is always decided in f64)."""
+        return self._relu_decide("pg_sig2_decide", genomes, k, genome_index)
 
     def _relu_decide(self, entry: str, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor]):
         dev = self.device

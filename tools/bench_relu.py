@@ -1,6 +1,7 @@
 """Measure Evaluator.evaluate alone on ReLU networks: k_relu against the general
 kernel (the only other way to run the workload), and the sigmoid k_service on
-the same genomes for context.  One JSON line per run.
+the same genomes for context; also the two-hidden-layer sigmoid k_sig2 against
+the general and the wide kernel.  One JSON line per run.
 
 Workload: [6,64,3] networks, 6 self-play games per genome against a hall of
 pop // 4, genes N(0, 3) drawn as bench.py's default workload draws them
@@ -14,6 +15,13 @@ interquartile range) of >= 20 launches are reported.
     python tools/bench_relu.py --shape 6 64 64 3 --runs relu2:4096 general:4096   # k_relu2
     python tools/bench_relu.py --shape 6 512 512 3 --dtype float32 --launches 5 \
         --runs relu_wide:4096 general:4096                                        # k_wide's ReLU instances (4.2e)
+    python tools/bench_relu.py --shape 6 64 64 3 --activation sigmoid \
+        --runs sig2:4096 general:4096 wide:4096                                   # k_sig2
+
+--activation sets the activation of the general and wide runs (default relu;
+relu, relu2 and relu_wide runs are always ReLU, sig2 and service runs always
+sigmoid).  --genes uniform draws U[0, 1) genes (generation 0 of a reference
+run, ga.py:85) instead of N(0, 3).
 
 relu_wide runs also report the network passes (counter [7]) and the streaming
 rate passes x gene bytes / launch time, as bench.py --config wide does for the
@@ -37,8 +45,11 @@ SHAPE = [6, 64, 3]
 RUNS = ["relu:4096", "general:4096", "relu:65536", "service:65536"]
 
 
-def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64):
+def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64, genes="normal"):
     G = sum((shape[i] + 1) * shape[i + 1] for i in range(len(shape) - 1))
+    if genes == "uniform":
+        return tuple(torch.rand((n, G), generator=torch.Generator(device=dev).manual_seed(sd), dtype=dtype, device=dev)
+                     for n, sd in ((pop, seed), (max(pop // 4, 1), seed + 1)))
     genomes = torch.randn((pop, G), generator=torch.Generator(device=dev).manual_seed(seed), dtype=dtype,
                           device=dev).mul_(sigma)
     hall = torch.randn((max(pop // 4, 1), G), generator=torch.Generator(device=dev).manual_seed(seed + 1),
@@ -47,15 +58,17 @@ def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64):
 
 
 KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu_wide": "k_wide<relu>", "general": "k_general",
-                "service": "k_service"}
+                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide"}
+FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid",
+                    "wide": "sigmoid"}
 
 
-def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64):
-    activation = "sigmoid" if name == "service" else "relu"
+def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, activation="relu", genes="normal"):
+    activation = FIXED_ACTIVATION.get(name, activation)
     kernel = "split" if name == "service" else name
     ev = Evaluator(shape, device=dev, dtype=dtype, activation=activation, kernel=kernel,
                    precision="f64" if name == "general" else "certified")
-    genomes, hall = workload(pop, dev, shape=shape, dtype=dtype)
+    genomes, hall = workload(pop, dev, shape=shape, dtype=dtype, genes=genes)
     sched = ev.selfplay_schedule(pop, hall.shape[0])
     res = None
     for _ in range(warmup):
@@ -81,7 +94,11 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64):
             "ms_iqr": round(float(q3 - q1), 4), "stepped_env_steps": int(c[0]), "episode_frames": frames,
             "stepped_env_steps_per_s": round(int(c[0]) / (med * 1e-3), 1), "forwards": int(c[1]),
             "f64_forwards": int(c[2]), "f64_share": round(int(c[2]) / max(int(c[1]), 1), 6),
+            "genes": "U[0,1)" if genes == "uniform" else "N(0,3)",
             "device": torch.cuda.get_device_name(dev)}
+    if name == "sig2":  # the cascade: forwards the f32 certificate left undecided (counter [4])
+        out["stage1_failures"] = int(c[4])
+        out["stage1_failure_share"] = round(int(c[4]) / max(int(c[1]), 1), 6)
     if name == "relu_wide":  # each network pass streams one network's genes once
         gene_bytes = ev.genes * genomes.element_size()
         out["network_passes"] = int(c[7])
@@ -93,12 +110,15 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64):
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, general, service")
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service")
     p.add_argument("--shape", nargs="+", type=int, default=SHAPE,
                    help="NETWORK_SHAPE (default 6 64 3; relu2 needs two hidden layers, e.g. 6 64 64 3)")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--launches", type=int, default=20, help="timed launches (>= 20; >= 5 for layers wider than 256)")
     p.add_argument("--dtype", default="float64", choices=["float64", "float32"], help="genome storage type")
+    p.add_argument("--activation", default="relu", choices=["relu", "sigmoid"],
+                   help="activation of the general runs (the other kernels have one activation each)")
+    p.add_argument("--genes", default="normal", choices=["normal", "uniform"], help="N(0, 3) genes or U[0, 1)")
     args = p.parse_args()
     if args.launches < (5 if max(args.shape[1:-1]) > 256 else 20):
         p.error("--launches must be >= 20 (>= 5 for layers wider than 256: seconds per launch)")
@@ -108,7 +128,7 @@ def main():
         if name not in KERNEL_NAMES:
             p.error(f"unknown kernel {name!r}")
         print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches, args.shape,
-                             getattr(torch, args.dtype))), flush=True)
+                             getattr(torch, args.dtype), args.activation, args.genes)), flush=True)
 
 
 if __name__ == "__main__":
