@@ -1,0 +1,269 @@
+// pg_certgame.hpp -- what the certified f32 kernel families share: k_relu
+// (pg_relu.hip), k_relu2 (pg_relu2.hip) and k_sig2 (pg_sig2.hip) are thin
+// __global__ wrappers of the one game loop cert_game<P>, and k_relu_decide,
+// k_relu2_decide and k_sig2_decide of the one pass cert_decide_pass<P>.
+// DESIGN.md 4.2g.
+//
+// A policy P describes one instance of a family to both bodies:
+//   LN, O, WT        lanes per network (a half-group), outputs, genome type
+//   kF64Stage        the stage that means "recomputed in f64": 1 where the
+//                    stages are 0/1 (k_relu, k_relu2), 3 for k_sig2's 0..3
+//   Net              a network's weights and bound as f32 in VGPRs; Net::e is
+//                    the bound pg_*_decide reports
+//   Lds              one half-group's __shared__ element
+//   load(net, g, dims, lds, hl)       this lane's share of genome g, in place
+//   decide(net, g, dims, k, live, lds, hl, z, stage)   one frame's np.argmax
+//                    index on the doubled-centroid features k; z: the f32
+//                    output pre-activations, stage: see kF64Stage
+// The host side below (the dispatch over O and the genome type, grid sizes,
+// pg_*_decide's parameters) serves the three .hip files.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+
+#include "../../include/pong_ga.h"
+#include "pg_cascade.hpp"
+#include "pg_device.hpp"
+#include "pg_eval.hpp"
+
+namespace pg {
+
+// the hidden sizes of a network: H2 is unused by the one-hidden-layer family
+struct CertDims {
+  int H1, H2;
+};
+
+// pg_relu_decide's, pg_relu2_decide's and pg_sig2_decide's parameters
+struct CertDecideParams {
+  const void *genomes;
+  const int32_t *gidx;
+  const int32_t *k;
+  int32_t *index;
+  int32_t *stage;
+  float *z32;
+  float *bound;
+  int64_t gstride;
+  int n, H1, H2;
+};
+
+// evaluate() (main.py:28-66): an aligned group of 2 LN lanes plays one game to
+// its end, taking games from the p.work queue; lanes [0, LN) hold the right
+// paddle's network (the genome), lanes [LN, 2 LN) the left paddle's (a
+// hall-of-fame row; idle against the scripted opponents and the ROM CPU).
+// Every lane of a group steps the same Pong state, and every frame is stepped.
+template <class P>
+__device__ __forceinline__ void cert_game(const EvalParams &params) {
+  // a copy of this function's own: its fields are values from here on.  Read
+  // through the reference they stay loads of unknown memory until this body is
+  // inlined into its kernel, and the kernels then come out differently
+  // scheduled.
+  const EvalParams p = params;
+  using WT = typename P::WT;
+  constexpr int LN = P::LN, O = P::O, L = 2 * LN, HPB = 256 / LN;
+  __shared__ typename P::Lds lds_all[HPB];
+  const int lane = threadIdx.x & 63;
+  const int lig = threadIdx.x & (L - 1);
+  const int half = lig / LN, hl = lig & (LN - 1);
+  const int leader = lane & ~(L - 1);
+  typename P::Lds &lds = lds_all[threadIdx.x / LN];
+  const WT *genomes = (const WT *)p.genomes;
+  const WT *opponents = (const WT *)p.opponents;
+  const CertDims dims = {p.nodes[1], p.nodes[2]};
+  const int games_total = active_total(p);
+  // per lane: far below 2^32.  c_fail (stage > 0) is c_f64 itself where the
+  // stages are 0/1: a counter of its own there costs the frame loop registers
+  uint32_t c_steps = 0, c_fwd = 0, c_fail = 0, c_f64 = 0, c_games = 0;
+
+  bool have = false, more = true;  // a game in play; the queue may hold more
+  int w = 0, kind = 0;
+  bool live = false;  // this half's network plays (the left half: only against a hall-of-fame row)
+  const WT *g = genomes;
+  typename P::Net net = {};  // (P::load updates it in place)
+  Pong st;
+  int act_r = 0, act_l = 0, timeout = 0, total = 0, frames = 0;
+  for (;;) {
+    if (!have && more) {
+      int ww = 0;
+      if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
+      w = group_broadcast<L>(ww, leader);
+      if (w < games_total) {
+        const int i = w / p.n_games, gi = w % p.n_games;
+        kind = p.kind[w];
+        const WT *gr = genomes + (long)genome_row(p, i) * p.gstride;
+        const WT *gl = (kind == kOppNN) ? opponents + (long)p.opp[w] * p.ostride : gr;
+        g = half ? gl : gr;
+        live = half == 0 || kind == kOppNN;
+        P::load(net, g, dims, lds, hl);
+        st.reset(game_seed(p.seed, gi), kind == kOppRomCpu);
+        act_r = act_l = timeout = total = frames = 0;
+        have = true;
+      } else {
+        more = false;
+      }
+    }
+    if (__builtin_amdgcn_ballot_w64(have) == 0) break;
+    if (have) {
+      const int s1b = st.s1, s2b = st.s2;
+      const int pvis = st.vis, pbx2 = 2 * st.bx + kBallW - 1, pby2 = 2 * st.by + kBallH - 1;
+      st.step(act_r, act_l);
+      frames += 1;
+      const int vis = st.vis;
+      const int bx2 = 2 * st.bx + kBallW - 1, by2 = 2 * st.by + kBallH - 1;
+      const int lc2 = paddle_c2(st.lpy), rc2 = paddle_c2(st.rpy);
+      int left = 0, right = 0;
+      if (PG_ANY(vis) && vis) {  // get_actions main.py:143-150
+        const int lbx2 = pvis ? pbx2 : bx2, lby2 = pvis ? pby2 : by2;
+        // utils.inference's features (utils.py:139-153) as doubled centroids: the left
+        // paddle sees the field mirrored, (160 - x) / 160 = (320 - 2x) / 320 exactly
+        int k[6];
+        k[0] = half ? 320 - bx2 : bx2;
+        k[1] = by2;
+        k[2] = half ? 320 - lbx2 : lbx2;
+        k[3] = lby2;
+        k[4] = half ? lc2 : rc2;
+        k[5] = half ? rc2 : lc2;
+        float z[O];
+        int stage;
+        const int mine = index_to_code(P::decide(net, g, dims, k, live, lds, hl, z, stage));
+        const int other = other_half<L>(mine);
+        right = half ? other : mine;
+        left = half ? mine : other;
+        c_fwd += live ? 1 : 0;
+        if constexpr (P::kF64Stage != 1) c_fail += stage > 0 ? 1 : 0;
+        c_f64 += stage == P::kF64Stage ? 1 : 0;
+        if (kind == kOppScore)
+          left = (st.s1 <= st.s2) ? hardcoded(by2, lc2) : 0;
+        else if (kind != kOppNN)
+          left = hardcoded(by2, lc2);
+      }
+      act_l = clamp_action(lc2, left);
+      act_r = clamp_action(rc2, right);
+      if (p.trace && w < p.trace_games && frames <= p.trace_cap && lig == 0)
+        p.trace[(long)w * p.trace_cap + frames - 1] = (uint8_t)(act_r | (act_l << 2) | (vis << 4));
+      if (frames > 1) {  // calculate_timeout_and_frames main.py:128-135
+        if (st.s1 == s1b && st.s2 == s2b) {
+          timeout += 1;
+        } else {
+          total += timeout;
+          timeout = 0;
+        }
+      }
+      if (st.s1 >= p.win_score || st.s2 >= p.win_score || st.done() || timeout > p.timeout_thresh) {
+        c_steps += frames;
+        c_games += 1;
+        if (lig == 0) finish_game(p, w, st, frames, total);
+        have = false;
+      }
+    }
+  }
+  if (p.counters) {
+    if (lig == 0 && c_games) {
+      atomicAdd((unsigned long long *)&p.counters[0], (unsigned long long)c_steps);
+      atomicAdd((unsigned long long *)&p.counters[3], (unsigned long long)c_games);
+    }
+    if (hl == 0 && c_fwd) {  // one lane per half-group: its network's forwards
+      atomicAdd((unsigned long long *)&p.counters[1], (unsigned long long)c_fwd);
+      // [2] the f64 forwards, [4] the frames the f32 certificate left undecided
+      if constexpr (P::kF64Stage == 1) {
+        if (c_f64) {
+          atomicAdd((unsigned long long *)&p.counters[2], (unsigned long long)c_f64);
+          atomicAdd((unsigned long long *)&p.counters[4], (unsigned long long)c_f64);
+        }
+      } else {
+        if (c_fail) atomicAdd((unsigned long long *)&p.counters[4], (unsigned long long)c_fail);
+        if (c_f64) atomicAdd((unsigned long long *)&p.counters[2], (unsigned long long)c_f64);
+      }
+    }
+  }
+}
+
+// pg_*_decide: the decision code of a cert_game frame, one half-group per
+// pass; a block's pass decides rows [base, base + 256 / LN).  The grid-stride
+// loop over base is the kernels' own: with the loop in here, inlining moves a
+// kernel's exit block and with it the instruction counts.
+template <class P>
+__device__ __forceinline__ void cert_decide_pass(const CertDecideParams &p, long base) {
+  using WT = typename P::WT;
+  constexpr int LN = P::LN, O = P::O, HPB = 256 / LN;
+  __shared__ typename P::Lds lds_all[HPB];
+  const int hg = threadIdx.x / LN, hl = threadIdx.x & (LN - 1);
+  const WT *genomes = (const WT *)p.genomes;
+  const CertDims dims = {p.H1, p.H2};
+  const long t = base + hg;
+  if (t < p.n) {
+    const WT *g = genomes + (long)(p.gidx ? p.gidx[t] : t) * p.gstride;
+    typename P::Net net = {};  // (P::load updates it in place)
+    P::load(net, g, dims, lds_all[hg], hl);
+    int k[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) k[i] = p.k[t * 6 + i];
+    float z[O];
+    int stage;
+    const int idx = P::decide(net, g, dims, k, true, lds_all[hg], hl, z, stage);
+    if (hl == 0) {
+      p.index[t] = idx;
+      if (p.stage) p.stage[t] = stage;
+      if (p.bound) p.bound[t] = net.e;
+      if (p.z32) {
+#pragma unroll
+        for (int o = 0; o < O; ++o) p.z32[t * O + o] = z[o];
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------ host side ----
+// Launch KERNEL<LN, UNITS..., O, WT> for the runtime O in 2..4 and genome type;
+// UNITS: the family's per-lane unit counts, in parentheses.
+#define PG_CERT_UNITS(...) __VA_ARGS__
+#define PG_CERT_DISPATCH(KERNEL, LN, UNITS, O, f64, grid, s, p)                                                    \
+  do {                                                                                                             \
+    if (O == 2) {                                                                                                  \
+      if (f64) hipLaunchKernelGGL((KERNEL<LN, PG_CERT_UNITS UNITS, 2, double>), dim3(grid), dim3(256), 0, s, p);  \
+      else hipLaunchKernelGGL((KERNEL<LN, PG_CERT_UNITS UNITS, 2, float>), dim3(grid), dim3(256), 0, s, p);       \
+    } else if (O == 3) {                                                                                           \
+      if (f64) hipLaunchKernelGGL((KERNEL<LN, PG_CERT_UNITS UNITS, 3, double>), dim3(grid), dim3(256), 0, s, p);  \
+      else hipLaunchKernelGGL((KERNEL<LN, PG_CERT_UNITS UNITS, 3, float>), dim3(grid), dim3(256), 0, s, p);       \
+    } else {                                                                                                       \
+      if (f64) hipLaunchKernelGGL((KERNEL<LN, PG_CERT_UNITS UNITS, 4, double>), dim3(grid), dim3(256), 0, s, p);  \
+      else hipLaunchKernelGGL((KERNEL<LN, PG_CERT_UNITS UNITS, 4, float>), dim3(grid), dim3(256), 0, s, p);       \
+    }                                                                                                              \
+  } while (0)
+
+// blocks of a game launch: a group of 2 LN lanes per game, at most two blocks per CU
+inline int cert_game_grid(const EvalParams &p, int LN) {
+  const int GPB = 256 / (2 * LN);
+  const int want = (p.total + GPB - 1) / GPB;
+  const int cap = num_cus() * 2;
+  return want < cap ? want : cap;
+}
+
+// blocks of a decide launch: a half-group of LN lanes per pass
+inline int cert_decide_grid(int n, int LN) {
+  const int HPB = 256 / LN;
+  const int want = (n + HPB - 1) / HPB;
+  const int cap = num_cus() * 8;
+  return want < cap ? want : cap;
+}
+
+inline CertDecideParams cert_decide_params(const pg_relu_decide_args *a, int H1, int H2) {
+  CertDecideParams p;
+  memset(&p, 0, sizeof(p));
+  p.genomes = a->genomes;
+  p.gidx = a->genome_index;
+  p.k = a->k;
+  p.index = a->index;
+  p.stage = a->stage;
+  p.z32 = a->z32;
+  p.bound = a->bound;
+  p.gstride = a->genome_stride;
+  p.n = a->n;
+  p.H1 = H1;
+  p.H2 = H2;
+  return p;
+}
+
+}  // namespace pg

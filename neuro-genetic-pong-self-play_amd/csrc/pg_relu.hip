@@ -14,161 +14,50 @@
 //                         network's static bound (pg_relu.hpp), and for the
 //                         undecided half-groups the f64 forward in numpy's order
 //                         from the genes.  Every frame is stepped.
-// DESIGN.md 4.2c.
+// The game loop and the decide pass are the certified families' shared ones
+// (pg_certgame.hpp); this file holds k_relu's policy and its host side.
+// DESIGN.md 4.2c, 4.2g.
 #include <hip/hip_runtime.h>
-
-#include <cstring>
 
 #include "../../include/pong_ga.h"
 #include "pg_cascade.hpp"
+#include "pg_certgame.hpp"
 #include "pg_device.hpp"
 #include "pg_eval.hpp"
 #include "pg_relu.hpp"
 
 namespace pg {
 
+// k_relu's policy (pg_certgame.hpp): U hidden units per lane, the half-group's
+// LDS is its f64 forward's LN * U hidden + O outputs
+template <int LN_, int U, int O_, typename WT_>
+struct ReluPolicy {
+  static constexpr int LN = LN_, O = O_, kF64Stage = 1;
+  using WT = WT_;
+  using Net = ReluNet<U, O>;
+  struct Lds {
+    double d[LN * U + 4];
+  };
+  static __device__ __forceinline__ void load(Net &net, const WT *g, const CertDims &dims, Lds &, int hl) {
+    relu_load<LN, U, O, WT>(net, g, dims.H1, hl);
+  }
+  static __device__ __forceinline__ int decide(const Net &net, const WT *g, const CertDims &dims, const int k[6],
+                                               bool live, Lds &lds, int hl, float z[O], int &stage) {
+    return relu_decide<LN, U, O, WT>(net, g, dims.H1, k, live, lds.d, hl, z, stage);
+  }
+};
+
 template <int LN, int U, int O, typename WT>
 __global__ __launch_bounds__(256, O <= 3 ? 2 : 1) void k_relu(EvalParams p) {
-  constexpr int L = 2 * LN, HPB = 256 / LN;
-  static_assert(L >= 8 && L <= 32, "other_half / group_broadcast layouts");
-  __shared__ double f64buf[HPB][LN * U + 4];  // a half-group's f64 forward: LN * U hidden + O outputs
-  const int lane = threadIdx.x & 63;
-  const int lig = threadIdx.x & (L - 1);
-  const int half = lig / LN, hl = lig & (LN - 1);
-  const int leader = lane & ~(L - 1);
-  double *lds = f64buf[threadIdx.x / LN];
-  const WT *genomes = (const WT *)p.genomes;
-  const WT *opponents = (const WT *)p.opponents;
-  const int H = p.nodes[1];
-  const int games_total = active_total(p);
-  uint32_t c_steps = 0, c_fwd = 0, c_slow = 0, c_games = 0;  // per lane: far below 2^32
-
-  bool have = false, more = true;  // a game in play; the queue may hold more
-  int w = 0, kind = 0;
-  bool live = false;  // this half's network plays (the left half: only against a hall-of-fame row)
-  const WT *g = genomes;
-  ReluNet<U, O> net = {};  // (relu_load updates it in place)
-  Pong st;
-  int act_r = 0, act_l = 0, timeout = 0, total = 0, frames = 0;
-  for (;;) {
-    if (!have && more) {
-      int ww = 0;
-      if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
-      w = group_broadcast<L>(ww, leader);
-      if (w < games_total) {
-        const int i = w / p.n_games, gi = w % p.n_games;
-        kind = p.kind[w];
-        const WT *gr = genomes + (long)genome_row(p, i) * p.gstride;
-        const WT *gl = (kind == kOppNN) ? opponents + (long)p.opp[w] * p.ostride : gr;
-        g = half ? gl : gr;
-        live = half == 0 || kind == kOppNN;
-        relu_load<LN, U, O, WT>(net, g, H, hl);
-        st.reset(game_seed(p.seed, gi), kind == kOppRomCpu);
-        act_r = act_l = timeout = total = frames = 0;
-        have = true;
-      } else {
-        more = false;
-      }
-    }
-    if (__builtin_amdgcn_ballot_w64(have) == 0) break;
-    if (have) {
-      const int s1b = st.s1, s2b = st.s2;
-      const int pvis = st.vis, pbx2 = 2 * st.bx + kBallW - 1, pby2 = 2 * st.by + kBallH - 1;
-      st.step(act_r, act_l);
-      frames += 1;
-      const int vis = st.vis;
-      const int bx2 = 2 * st.bx + kBallW - 1, by2 = 2 * st.by + kBallH - 1;
-      const int lc2 = paddle_c2(st.lpy), rc2 = paddle_c2(st.rpy);
-      int left = 0, right = 0;
-      if (PG_ANY(vis) && vis) {  // get_actions main.py:143-150
-        const int lbx2 = pvis ? pbx2 : bx2, lby2 = pvis ? pby2 : by2;
-        // utils.inference's features (utils.py:139-153) as doubled centroids: the left
-        // paddle sees the field mirrored, (160 - x) / 160 = (320 - 2x) / 320 exactly
-        int k[6];
-        k[0] = half ? 320 - bx2 : bx2;
-        k[1] = by2;
-        k[2] = half ? 320 - lbx2 : lbx2;
-        k[3] = lby2;
-        k[4] = half ? lc2 : rc2;
-        k[5] = half ? rc2 : lc2;
-        float z[O];
-        int slow;
-        const int mine = index_to_code(relu_decide<LN, U, O, WT>(net, g, H, k, live, lds, hl, z, slow));
-        const int other = other_half<L>(mine);
-        right = half ? other : mine;
-        left = half ? mine : other;
-        c_fwd += live ? 1 : 0;
-        c_slow += slow;
-        if (kind == kOppScore)
-          left = (st.s1 <= st.s2) ? hardcoded(by2, lc2) : 0;
-        else if (kind != kOppNN)
-          left = hardcoded(by2, lc2);
-      }
-      act_l = clamp_action(lc2, left);
-      act_r = clamp_action(rc2, right);
-      if (p.trace && w < p.trace_games && frames <= p.trace_cap && lig == 0)
-        p.trace[(long)w * p.trace_cap + frames - 1] = (uint8_t)(act_r | (act_l << 2) | (vis << 4));
-      if (frames > 1) {  // calculate_timeout_and_frames main.py:128-135
-        if (st.s1 == s1b && st.s2 == s2b) {
-          timeout += 1;
-        } else {
-          total += timeout;
-          timeout = 0;
-        }
-      }
-      if (st.s1 >= p.win_score || st.s2 >= p.win_score || st.done() || timeout > p.timeout_thresh) {
-        c_steps += frames;
-        c_games += 1;
-        if (lig == 0) finish_game(p, w, st, frames, total);
-        have = false;
-      }
-    }
-  }
-  if (p.counters) {
-    if (lig == 0 && c_games) {
-      atomicAdd((unsigned long long *)&p.counters[0], (unsigned long long)c_steps);
-      atomicAdd((unsigned long long *)&p.counters[3], (unsigned long long)c_games);
-    }
-    if (hl == 0 && c_fwd) {  // one lane per half-group: its network's forwards
-      atomicAdd((unsigned long long *)&p.counters[1], (unsigned long long)c_fwd);
-      if (c_slow) {
-        atomicAdd((unsigned long long *)&p.counters[2], (unsigned long long)c_slow);
-        atomicAdd((unsigned long long *)&p.counters[4], (unsigned long long)c_slow);
-      }
-    }
-  }
+  static_assert(2 * LN >= 8 && 2 * LN <= 32, "other_half / group_broadcast layouts");
+  cert_game<ReluPolicy<LN, U, O, WT>>(p);
 }
 
-// pg_relu_decide: one half-group per pass, the decision code of a k_relu frame.
 template <int LN, int U, int O, typename WT>
-__global__ __launch_bounds__(256) void k_relu_decide(ReluDecideParams p) {
+__global__ __launch_bounds__(256) void k_relu_decide(CertDecideParams p) {
   constexpr int HPB = 256 / LN;
-  __shared__ double f64buf[HPB][LN * U + 4];
-  const int hg = threadIdx.x / LN, hl = threadIdx.x & (LN - 1);
-  const WT *genomes = (const WT *)p.genomes;
-  for (long base = (long)blockIdx.x * HPB; base < p.n; base += (long)gridDim.x * HPB) {
-    const long t = base + hg;
-    if (t < p.n) {
-      const WT *g = genomes + (long)(p.gidx ? p.gidx[t] : t) * p.gstride;
-      ReluNet<U, O> net = {};  // (relu_load updates it in place)
-      relu_load<LN, U, O, WT>(net, g, p.H, hl);
-      int k[6];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) k[i] = p.k[t * 6 + i];
-      float z[O];
-      int slow;
-      const int idx = relu_decide<LN, U, O, WT>(net, g, p.H, k, true, f64buf[hg], hl, z, slow);
-      if (hl == 0) {
-        p.index[t] = idx;
-        if (p.stage) p.stage[t] = slow;
-        if (p.bound) p.bound[t] = net.e;
-        if (p.z32) {
-#pragma unroll
-          for (int o = 0; o < O; ++o) p.z32[t * O + o] = z[o];
-        }
-      }
-    }
-  }
+  for (long base = (long)blockIdx.x * HPB; base < p.n; base += (long)gridDim.x * HPB)
+    cert_decide_pass<ReluPolicy<LN, U, O, WT>>(p, base);
 }
 
 bool relu_shape_ok(const pg_net &n) {
@@ -177,19 +66,14 @@ bool relu_shape_ok(const pg_net &n) {
 }
 
 // the instances: LN = relu_lanes(H) lanes per network, kReluUnits units per lane
-#define PG_RELU_DISPATCH(KERNEL, LN, O, f64, grid, s, p)                                                     \
-  do {                                                                                                       \
-    if (O == 2) {                                                                                            \
-      if (f64) hipLaunchKernelGGL((KERNEL<LN, kReluUnits, 2, double>), dim3(grid), dim3(256), 0, s, p);     \
-      else hipLaunchKernelGGL((KERNEL<LN, kReluUnits, 2, float>), dim3(grid), dim3(256), 0, s, p);          \
-    } else if (O == 3) {                                                                                     \
-      if (f64) hipLaunchKernelGGL((KERNEL<LN, kReluUnits, 3, double>), dim3(grid), dim3(256), 0, s, p);     \
-      else hipLaunchKernelGGL((KERNEL<LN, kReluUnits, 3, float>), dim3(grid), dim3(256), 0, s, p);          \
-    } else {                                                                                                 \
-      if (f64) hipLaunchKernelGGL((KERNEL<LN, kReluUnits, 4, double>), dim3(grid), dim3(256), 0, s, p);     \
-      else hipLaunchKernelGGL((KERNEL<LN, kReluUnits, 4, float>), dim3(grid), dim3(256), 0, s, p);          \
-    }                                                                                                        \
+#define PG_RELU_DISPATCH(KERNEL, LN, O, f64, grid, s, p)                            \
+  do {                                                                              \
+    if (LN == 4) PG_CERT_DISPATCH(KERNEL, 4, (kReluUnits), O, f64, grid, s, p);     \
+    else if (LN == 8) PG_CERT_DISPATCH(KERNEL, 8, (kReluUnits), O, f64, grid, s, p); \
+    else PG_CERT_DISPATCH(KERNEL, 16, (kReluUnits), O, f64, grid, s, p);            \
   } while (0)
+
+static long relu_genes(int H, int O) { return (long)H * 7 + (long)O * (H + 1); }
 
 int32_t launch_relu(const EvalParams &p, int dtype, hipStream_t s) {
   const int H = p.nodes[1], O = p.nodes[2];
@@ -197,17 +81,12 @@ int32_t launch_relu(const EvalParams &p, int dtype, hipStream_t s) {
     return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
   const int LN = relu_lanes(H);
   if (LN * kReluUnits < H) return fail(PG_ERR_UNSUPPORTED, "relu kernel: no layout for H=%d", H);
-  if (p.gstride < (long)H * 7 + (long)O * (H + 1) || (p.n_opponents > 0 && p.ostride < (long)H * 7 + (long)O * (H + 1)))
+  const long G = relu_genes(H, O);
+  if (p.gstride < G || (p.n_opponents > 0 && p.ostride < G))
     return fail(PG_ERR_INVALID, "relu kernel: a row stride is below the gene count");
-  const int GPB = 256 / (2 * LN);
-  const int want = (p.total + GPB - 1) / GPB;
-  const int cap = num_cus() * 2;
-  const int grid = want < cap ? want : cap;
+  const int grid = cert_game_grid(p, LN);
   if (grid <= 0) return PG_OK;
-  const bool f64 = dtype == PG_F64;
-  if (LN == 4) PG_RELU_DISPATCH(k_relu, 4, O, f64, grid, s, p);
-  else if (LN == 8) PG_RELU_DISPATCH(k_relu, 8, O, f64, grid, s, p);
-  else PG_RELU_DISPATCH(k_relu, 16, O, f64, grid, s, p);
+  PG_RELU_DISPATCH(k_relu, LN, O, dtype == PG_F64, grid, s, p);
   PG_HIP(hipGetLastError());
   return PG_OK;
 }
@@ -227,32 +106,15 @@ extern "C" int32_t pg_relu_decide(const pg_relu_decide_args *a, void *stream) {
   if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);
   if (a->n == 0) return PG_OK;
   const int H = a->net.nodes[1], O = a->net.nodes[2];
-  const long G = (long)H * 7 + (long)O * (H + 1);
+  const long G = relu_genes(H, O);
   if (!a->genomes || a->genome_stride < G || !a->k || !a->index)
     return fail(PG_ERR_INVALID, "genomes/k/index NULL or genome_stride < gene count %ld", G);
   const int LN = relu_lanes(H);
   if (LN * kReluUnits < H) return fail(PG_ERR_UNSUPPORTED, "pg_relu_decide: no layout for H=%d", H);
-  ReluDecideParams p;
-  memset(&p, 0, sizeof(p));
-  p.genomes = a->genomes;
-  p.gidx = a->genome_index;
-  p.k = a->k;
-  p.index = a->index;
-  p.stage = a->stage;
-  p.z32 = a->z32;
-  p.bound = a->bound;
-  p.gstride = a->genome_stride;
-  p.n = a->n;
-  p.H = H;
-  const int HPB = 256 / LN;
-  const int want = (a->n + HPB - 1) / HPB;
-  const int cap = num_cus() * 8;
-  const int grid = want < cap ? want : cap;
-  const bool f64 = a->net.dtype == PG_F64;
+  const CertDecideParams p = cert_decide_params(a, H, 0);
+  const int grid = cert_decide_grid(a->n, LN);
   hipStream_t s = (hipStream_t)stream;
-  if (LN == 4) PG_RELU_DISPATCH(k_relu_decide, 4, O, f64, grid, s, p);
-  else if (LN == 8) PG_RELU_DISPATCH(k_relu_decide, 8, O, f64, grid, s, p);
-  else PG_RELU_DISPATCH(k_relu_decide, 16, O, f64, grid, s, p);
+  PG_RELU_DISPATCH(k_relu_decide, LN, O, a->net.dtype == PG_F64, grid, s, p);
   PG_HIP(hipGetLastError());
   return PG_OK;
 }

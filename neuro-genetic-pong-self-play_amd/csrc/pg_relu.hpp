@@ -198,17 +198,4 @@ __device__ __forceinline__ int relu_decide(const ReluNet<U, O> &n, const WT *__r
   return idx < 0 ? 0 : idx;
 }
 
-// pg_relu_decide's parameters (k_relu_decide)
-struct ReluDecideParams {
-  const void *genomes;
-  const int32_t *gidx;
-  const int32_t *k;
-  int32_t *index;
-  int32_t *stage;
-  float *z32;
-  float *bound;
-  int64_t gstride;
-  int n, H;
-};
-
 }  // namespace pg

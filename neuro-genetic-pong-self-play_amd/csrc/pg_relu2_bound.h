@@ -1,5 +1,5 @@
 /* pg_relu2_bound.h -- the static f32 error bound of k_relu2's certificate
- * (pg_relu2.hpp), in plain C so that it compiles for the device and for the
+ * (pg_hidden2.hpp), in plain C so that it compiles for the device and for the
  * host alike (tests/test_relu2_host.py runs it under gcc).
  *
  * The network [6, H1, H2, O] with bias, inputs x_i = k_i / 320 in [0, 1]:
@@ -18,7 +18,7 @@
  *            (padded) layer-1 unit, <= 64, onto the bias
  *   layer 3  PG_RELU2_CHAIN3 = 11:  1 (gene) + a lane's <= 4 units + the sum
  *            over <= 32 lanes (5 steps) + the bias
- * (pg_relu2.hpp asserts that every instantiated layout stays within them).
+ * (pg_hidden2.hpp asserts that every instantiated layout stays within them).
  *
  * With  A_j = sum_i |W1_ji| + |b1_j|           (>= |z1_j|, as x_i <= 1)
  *       B_k = sum_j |W2_kj| A_j + |b2_k|       (>= |z2_k|)

@@ -1,5 +1,5 @@
 /* pg_sig2_bound.h -- the static f32 error bound of k_sig2's certificate
- * (pg_sig2.hpp), in plain C so that it compiles for the device and for the
+ * (pg_hidden2.hpp), in plain C so that it compiles for the device and for the
  * host alike (tests/test_sig2_host.py runs it under gcc).
  *
  * The network [6, H1, H2, O] with bias, inputs x_i = k_i / 320 in [0, 1],
@@ -15,7 +15,7 @@
  * term of a computed dot product passes through at most c roundings (factors
  * 1 + d, |d| <= u = 2^-24), the result differs from the exact sum by at most
  * gamma_c sum_i |t_i|, gamma_c = c u / (1 - c u), whatever the order.  The
- * chain lengths are k_relu2's (the layout is the same; pg_sig2.hpp asserts that
+ * chain lengths are k_relu2's (the layout is the same; pg_hidden2.hpp asserts that
  * every instantiated layout stays within them):
  *   layer 1  PG_SIG2_CHAIN1 = 9:   1 (gene to f32) + 2 (the feature
  *            fl32(k * fl32(1 / 320)), feat32) + 6 fused multiply-adds

@@ -13,9 +13,10 @@
 //                         wave itself (8-lane groups) or a service wave.
 //   k_general<WT>         any NETWORK_SHAPE, one wave per game, f64 numpy_nn
 //                         arithmetic with activations staged in LDS (sigmoid or ReLU).
-//   k_relu<LN,U,O,WT>     [6, H<=256, O] ReLU networks (pg_relu.hip).
-//   k_relu2<LN,U1,U2,O,WT>  [6, H1<=64, H2<=64, O] ReLU networks (pg_relu2.hip).
-//   k_sig2<LN,U1,U2,O,WT>   [6, H1<=64, H2<=64, O] sigmoid networks (pg_sig2.hip).
+//   k_relu<LN,U,O,WT>     [6, H<=256, O] ReLU networks (pg_relu.hip, pg_relu.hpp).
+//   k_relu2<LN,U1,U2,O,WT>  [6, H1<=64, H2<=64, O] ReLU networks (pg_relu2.hip, pg_hidden2.hpp).
+//   k_sig2<LN,U1,U2,O,WT>   [6, H1<=64, H2<=64, O] sigmoid networks (pg_sig2.hip, pg_hidden2.hpp).
+//                         These three share one game loop (pg_certgame.hpp).
 //   k_fitness             sum(all_rewards) / GAMES_TO_PLAY in the reference order.
 //   k_forward_*           NeuralNetwork.run batched (parity entry point).
 //   k_physics_*           the SoA Pong stepper on its own.

@@ -10,8 +10,8 @@ from ._lib import LIB_PATH, PKG_DIR, REPO_DIR
 
 CSRC = os.path.join(PKG_DIR, "csrc")
 HEADERS = [os.path.join(CSRC, h) for h in ("pg_device.hpp", "pg_f64math.h", "pg_eval.hpp", "pg_cascade.hpp",
-                                           "pg_service.hpp", "pg_relu.hpp", "pg_relu_bound.h", "pg_relu2.hpp",
-                                           "pg_relu2_bound.h", "pg_sig2.hpp", "pg_sig2_bound.h")] + [os.path.join(REPO_DIR, "include", "pong_ga.h")]
+                                           "pg_service.hpp", "pg_certgame.hpp", "pg_relu.hpp", "pg_relu_bound.h",
+                                           "pg_hidden2.hpp", "pg_relu2_bound.h", "pg_sig2_bound.h")] + [os.path.join(REPO_DIR, "include", "pong_ga.h")]
 # one translation unit per kernel family, compiled in parallel and linked into one .so;
 # pg_service_more.hip is compiled once per (lanes per game, genome type): its ~100
 # k_service instantiations took 10 minutes as one unit

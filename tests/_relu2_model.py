@@ -1,4 +1,4 @@
-"""The host model of k_relu2's decision (csrc/pg_relu2.hpp, pg_relu2_bound.h) in
+"""The host model of k_relu2's decision (csrc/pg_hidden2.hpp, pg_relu2_bound.h) in
 plain numpy, shared by tests/test_relu2_host.py and tests/test_gpu_relu2.py:
 the f32 chain of a [6, H1, H2, O] ReLU network with the once-rounded fused
 multiply-add of tests/_relu_model.py, numpy_nn's f64 chain, the gcc-compiled
@@ -22,7 +22,7 @@ SHAPES = [[6, 2, 2, 2], [6, 5, 4, 2], [6, 16, 16, 3], [6, 17, 33, 4], [6, 64, 2,
 
 
 def lanes(H1, H2):
-    """relu2_lanes / relu2_units (pg_relu2.hpp): lanes per network, units of each layer per lane."""
+    """hidden2_lanes / hidden2_units (pg_hidden2.hpp): lanes per network, units of each layer per lane."""
     m = max(H1, H2)
     LN = 4 if m <= 16 else (16 if m <= 32 else 32)
     return LN, (4 if LN == 4 else 2)
@@ -72,7 +72,7 @@ def bounds(tmp_path, shape, nets):
 
 
 def z32(shape, g, k):
-    """k_relu2's f32 chain (pg_relu2.hpp relu2_z32) for genomes g [N, G] on doubled
+    """k_relu2's f32 chain (pg_hidden2.hpp hidden2_z32) for genomes g [N, G] on doubled
     centroids k [N, m, 6] -> [N, m, O]: layer 1 as six fmas onto the bias; layer
     2 one fma per padded layer-1 unit, in order, onto the bias; layer 3 a lane's
     units hl U + v in order from 0, a pairwise tree over the lanes (group_sum),

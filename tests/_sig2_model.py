@@ -1,4 +1,4 @@
-"""The host model of k_sig2's decision (csrc/pg_sig2.hpp, pg_sig2_bound.h) in
+"""The host model of k_sig2's decision (csrc/pg_hidden2.hpp, pg_sig2_bound.h) in
 plain numpy, shared by tests/test_sig2_host.py and tests/test_gpu_sig2.py: the
 f32 chain of a [6, H1, H2, O] sigmoid network on tests/_relu_model.py's
 once-rounded fused multiply-add with an emulated f32 sigmoid, numpy_nn's f64
@@ -91,7 +91,7 @@ def _sig32(a, d):
 
 
 def z32(shape, g, k, out=None, sign=0.0):
-    """k_sig2's f32 chain (pg_sig2.hpp sig2_z32) for genomes g [N, G] on doubled
+    """k_sig2's f32 chain (pg_hidden2.hpp hidden2_z32) for genomes g [N, G] on doubled
     centroids k [N, m, 6] -> [N, m, O]: layer 1 as six fmas onto the bias; layer
     2 one fma per padded layer-1 unit, in order, onto the bias; layer 3 a lane's
     units hl U + v in order from 0, a pairwise tree over the lanes (group_sum),

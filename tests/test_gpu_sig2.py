@@ -271,6 +271,26 @@ def test_sig2_groups_play_several_games(gpu, shape, n, dtype):
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all() and ch[3] == n * 6 and ch[2] <= ch[4] < ch[1]
 
 
+@pytest.mark.parametrize("shape", [[6, 2, 2, 2], [6, 17, 3, 3], [6, 33, 64, 4]], ids=_ids)
+def test_sig2_counter_flush(gpu, shape):
+    """The shared game loop's flush of a family whose stages are 0..3: [2] the
+    f64 forwards (stage 3) <= [4] the stage-1 failures (stage > 0) <= [1] the
+    forwards.  The smallest padded shape of each layout (4, 16, 32 lanes), 8
+    genomes x 2 games against hall rows so that both half-groups play; half of
+    the rows fail stage 1 at every forward."""
+    rng = np.random.default_rng(sum(shape) + 3)
+    G = M.genes(shape)
+    genomes = _dev_genomes(np.concatenate([rng.standard_normal((4, G)), _hard_rows(shape, rng, 4)]), gpu, torch.float64)
+    hall = _dev_genomes(np.concatenate([rng.standard_normal((2, G)), _hard_rows(shape, rng, 2)]), gpu, torch.float64)
+    sched = [torch.tensor(a, device=gpu) for a in (np.full((8, 2), 3, np.int32), rng.integers(0, 4, size=(8, 2)).astype(np.int32),
+                                                   np.ones((8, 2)))]
+    ev = _ev(shape, gpu, n_games=2, timeout_thresh=119, win_score=1)
+    res, _ = ev.evaluate(genomes, *sched, opponents=hall, kernel="sig2")
+    c = res.counters.cpu().numpy()
+    print(f"{shape}: forwards {c[1]}, stage-1 failures {c[4]}, f64 {c[2]}")
+    assert 0 < c[2] <= c[4] <= c[1]
+
+
 # ------------------------------------------------------------ 4 refusals ----
 def test_unsupported_combinations_are_refused(gpu):
     from pong_amd import _lib
