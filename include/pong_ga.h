@@ -146,10 +146,27 @@ typedef enum pg_kernel {
                               with sigmoid_f32 in both hidden layers, a static f32 bound through the two
                               sigmoid layers and k_service's decision cascade on the output pre-activations,
                               the rest recomputed in f64 in numpy's order.  Every frame is
-                              stepped (counters [8] = [12] = 0); no lane records, no workspace beyond the
+                              stepped (counters [8] = [12] = 0) unless PG_KERNEL_ADVANCE is set; no lane records, no workspace beyond the
                               base.  PG_ERR_UNSUPPORTED for a ReLU net, any other shape, no bias, PG_PREC_F64,
                               horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it */
 } pg_kernel;
+
+/* pg_eval_args.kernel holds a pg_kernel in its low byte and modifier bits above it (ABI 13).
+ * Any bit other than the ones named here: PG_ERR_INVALID. */
+enum {
+  PG_KERNEL_ADVANCE = 0x100 /* closed-form frame advance on the certified f32 families, opt-in:
+                               PG_KERNEL_RELU, PG_KERNEL_RELU2 and PG_KERNEL_SIG2 step every frame; with this bit
+                               OR-ed in they advance a serve delay's 29 hidden-ball frames at once (counters [12])
+                               and jump the rest of a rally proven periodic to its timeout frame (counters [8]),
+                               as SPLIT and WIDE always do -- every output bit for bit the stepping kernel's.
+                               The scope, the refusals and their messages are the base kernel's (horizon > 0
+                               and hard_log stay refused); the workspace is the same.  PG_KERNEL_AUTO with the
+                               bit resolves exactly as without it: where it picks RELU or RELU2 the advance is
+                               on, where it picks SPLIT, WIDE or GENERAL the bit changes nothing.  Every other
+                               explicit kernel with the bit: PG_ERR_UNSUPPORTED (checked, like the bits, even
+                               for an empty launch).  A launch with trace != NULL records every frame and so
+                               runs with the advance off, which is not an error ([8] = [12] = 0) */
+};
 
 /* pg_eval_args.prep: the SPLIT kernel's lane records (one per network of the
  * launch) in two halves, so a caller can prepare the genomes' records while
@@ -210,11 +227,15 @@ typedef struct pg_eval_args {
                                     kernels: [8] episode frames of periodic rallies advanced to their
                                     timeout at once; [9] hard decisions (see hard_log); split kernel:
                                     [12] serve-delay frames advanced at once (ball hidden); the
-                                    episodes' frames = [0] + [8] + [12]; [10], [11], [13..15] 0 */
+                                    episodes' frames = [0] + [8] + [12]; [10], [11], [13..15] 0.
+                                    RELU, RELU2 and SIG2 step every frame ([8] = [12] = 0) unless
+                                    PG_KERNEL_ADVANCE is set on an untraced launch: then [8] and [12]
+                                    count as for the split kernel, [0] the stepped frames only, and
+                                    [1], [2], [4] only the forwards actually run */
   uint8_t *trace;                /* optional [trace_games, trace_cap] per-frame action codes */
   int32_t trace_games;           /* games (genome-major index g = i*n_games + game) traced */
   int32_t trace_cap;
-  int32_t kernel;                /* pg_kernel */
+  int32_t kernel;                /* pg_kernel, optionally | PG_KERNEL_ADVANCE */
   int32_t group_lanes;           /* lanes per game of RESIDENT (4..64) / SPLIT (8..64), 0 = auto */
   void *workspace;               /* device scratch of pg_eval_workspace_bytes() bytes */
   size_t workspace_bytes;

@@ -76,7 +76,11 @@ ACTIVATION = "sigmoid"
 # two-hidden-layer sigmoid networks (ACTIVATION = "sigmoid", NETWORK_SHAPE
 # [6, 2..64, 2..64, 2..4], BIAS), which "auto" leaves on the general kernel (on
 # the wide one from 64 units up); a kernel that cannot run the configured
-# network is an error, never a fallback.
+# network is an error, never a fallback.  "relu+advance", "relu2+advance",
+# "sig2+advance" and "auto+advance" are the opt-in closed-form frame advance of
+# the certified f32 kernels (serve delays and periodic rallies are not stepped
+# frame by frame; the same results); "auto+advance" picks as
+# "auto" does and advances where that is the relu or the relu2 kernel.
 KERNEL = "auto"
 # Storage type of genomes on the device; float64 keeps Python floats exact.
 GENOME_DTYPE = "float64"

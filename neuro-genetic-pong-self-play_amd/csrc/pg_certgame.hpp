@@ -1,8 +1,9 @@
 // pg_certgame.hpp -- what the certified f32 kernel families share: k_relu
 // (pg_relu.hip), k_relu2 (pg_relu2.hip) and k_sig2 (pg_sig2.hip) are thin
-// __global__ wrappers of the one game loop cert_game<P>, and k_relu_decide,
-// k_relu2_decide and k_sig2_decide of the one pass cert_decide_pass<P>.
-// DESIGN.md 4.2g.
+// __global__ wrappers of the one game loop cert_game<P, kAdvance>, and
+// k_relu_decide, k_relu2_decide and k_sig2_decide of the one pass
+// cert_decide_pass<P>.  k_relu_adv, k_relu2_adv and k_sig2_adv wrap the same
+// loop with kAdvance on (PG_KERNEL_ADVANCE).  DESIGN.md 4.2g, 4.2h.
 //
 // A policy P describes one instance of a family to both bodies:
 //   LN, O, WT        lanes per network (a half-group), outputs, genome type
@@ -49,12 +50,41 @@ struct CertDecideParams {
   int n, H1, H2;
 };
 
+// kAdvance's per-group record: Brent's saved rally key, the no-score count it
+// was saved at (-1: no search open) and the span; the group's frames advanced
+// in closed form.  In LDS, written by the group's lane 0 and read only behind
+// the rare tests (a bounce past the kRallyHits-th return, a serve, the end), so
+// the common frame path holds none of it in registers.  The search's three
+// fields go through relaxed atomics (adv_ld / adv_st): the other lanes of the
+// group read what lane 0 wrote earlier in the wave's program order, which the
+// compiler must not replace by a value it read before.  (Not volatile: a
+// volatile access keeps its generic pointer, flat instructions and two more
+// VGPRs for the address across the frame loop.)
+struct CertAdvance {
+  uint64_t key;
+  int at, span;
+  uint32_t skipped, hidden;
+};
+template <class T>
+__device__ __forceinline__ T adv_ld(T *a) { return __hip_atomic_load(a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+template <class T>
+__device__ __forceinline__ void adv_st(T *a, T v) { __hip_atomic_store(a, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
+template <int N>
+__device__ __forceinline__ CertAdvance *cert_advance_lds() {
+  __shared__ CertAdvance adv[N];
+  return adv;
+}
+
 // evaluate() (main.py:28-66): an aligned group of 2 LN lanes plays one game to
 // its end, taking games from the p.work queue; lanes [0, LN) hold the right
 // paddle's network (the genome), lanes [LN, 2 LN) the left paddle's (a
 // hall-of-fame row; idle against the scripted opponents and the ROM CPU).
-// Every lane of a group steps the same Pong state, and every frame is stepped.
-template <class P>
+// Every lane of a group steps the same Pong state.  Every frame is stepped,
+// unless kAdvance (PG_KERNEL_ADVANCE, the k_*_adv wrappers; untraced launches
+// only): then a serve delay's hidden-ball frames and the rest of a rally proven
+// periodic are advanced in closed form, k_service's rules (pg_service.hpp,
+// DESIGN.md 4.2h) -- the same results, counters [12] and [8].
+template <class P, bool kAdvance>
 __device__ __forceinline__ void cert_game(const EvalParams &params) {
   // a copy of this function's own: its fields are values from here on.  Read
   // through the reference they stay loads of unknown memory until this body is
@@ -76,6 +106,14 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
   // per lane: far below 2^32.  c_fail (stage > 0) is c_f64 itself where the
   // stages are 0/1: a counter of its own there costs the frame loop registers
   uint32_t c_steps = 0, c_fwd = 0, c_fail = 0, c_f64 = 0, c_games = 0;
+  [[maybe_unused]] CertAdvance *adv = nullptr;  // this group's record (kAdvance)
+  if constexpr (kAdvance) {
+    adv = cert_advance_lds<256 / L>() + threadIdx.x / L;
+    if (lig == 0) {
+      adv_st(&adv->at, -1);
+      adv->skipped = adv->hidden = 0;
+    }
+  }
 
   bool have = false, more = true;  // a game in play; the queue may hold more
   int w = 0, kind = 0;
@@ -100,15 +138,43 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
         st.reset(game_seed(p.seed, gi), kind == kOppRomCpu);
         act_r = act_l = timeout = total = frames = 0;
         have = true;
+        // groups reload games in place: the last game's search must not survive
+        if constexpr (kAdvance) {
+          if (lig == 0) adv_st(&adv->at, -1);
+        }
       } else {
         more = false;
       }
     }
     if (__builtin_amdgcn_ballot_w64(have) == 0) break;
     if (have) {
+      if constexpr (kAdvance) {
+        // The serve delay in closed form (pg_service.hpp): while the ball is
+        // hidden no point can be scored, get_actions returns [0,0]
+        // (main.py:151-153) -- the pending actions are clamp-only already: the
+        // frame of a miss and a game's start decide nothing -- and a paddle only
+        // drifts back inside the clamp band (Pong::drift), so the frames before
+        // the serve frame are advanced at once.  The no-score counter cannot
+        // pass TIMEOUT_THRESH on the way: it is at most 0 + 29 here and
+        // pg_eval_population refuses a threshold below 32.
+        const bool hid = !st.vis && st.timer >= 2;
+        if (PG_ANY(hid) && hid) {
+          const int h = st.timer - 1;
+          st.rpy = Pong::drift(st.rpy, h);
+          if (!st.one_player) st.lpy = Pong::drift(st.lpy, h);
+          st.timer = 1;
+          act_r = clamp_action(paddle_c2(st.rpy), 0);
+          act_l = clamp_action(paddle_c2(st.lpy), 0);  // (a 1-player env's CPU paddle ignores it)
+          // a game's frame 1 does not count towards the no-score counter
+          // (main.py:128-135): after a start's 29 frames it stands at 28
+          timeout += frames ? h : h - 1;
+          frames += h;
+          if (lig == 0) adv->hidden += h;
+        }
+      }
       const int s1b = st.s1, s2b = st.s2;
       const int pvis = st.vis, pbx2 = 2 * st.bx + kBallW - 1, pby2 = 2 * st.by + kBallH - 1;
-      st.step(act_r, act_l);
+      [[maybe_unused]] const int ev = st.step(act_r, act_l);
       frames += 1;
       const int vis = st.vis;
       const int bx2 = 2 * st.bx + kBallW - 1, by2 = 2 * st.by + kBallH - 1;
@@ -141,14 +207,51 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
       }
       act_l = clamp_action(lc2, left);
       act_r = clamp_action(rc2, right);
-      if (p.trace && w < p.trace_games && frames <= p.trace_cap && lig == 0)
-        p.trace[(long)w * p.trace_cap + frames - 1] = (uint8_t)(act_r | (act_l << 2) | (vis << 4));
+      if constexpr (!kAdvance) {  // (a traced launch runs the stepping kernel)
+        if (p.trace && w < p.trace_games && frames <= p.trace_cap && lig == 0)
+          p.trace[(long)w * p.trace_cap + frames - 1] = (uint8_t)(act_r | (act_l << 2) | (vis << 4));
+      }
       if (frames > 1) {  // calculate_timeout_and_frames main.py:128-135
         if (st.s1 == s1b && st.s2 == s2b) {
           timeout += 1;
         } else {
           total += timeout;
           timeout = 0;
+          if constexpr (kAdvance) {
+            if (lig == 0) adv_st(&adv->at, -1);  // a point: the next rally searches afresh
+          }
+        }
+      }
+      if constexpr (kAdvance) {
+        // A periodic rally ends at the timeout with nothing else changed: jump
+        // there.  Brent's cycle search as k_service runs it (pg_service.hpp),
+        // sampled at the frames where a paddle returned the ball, from the
+        // point's kRallyHits-th return on (rally_key caps hits there, so no
+        // earlier state of the point can recur): a key equal to the saved one
+        // proves the rally periodic; the save moves forward when the distance
+        // reaches the span (kRallySpan0 frames, doubling).
+        const bool check = ev == kStepBounce && st.hits >= kRallyHits && timeout <= p.timeout_thresh;
+        if (PG_ANY(check) && check) {
+          const uint64_t key = rally_key(st, act_r, act_l);
+          const int at = adv_ld(&adv->at);
+          if (at < 0 || at > timeout) {
+            if (lig == 0) {
+              adv_st(&adv->key, key);
+              adv_st(&adv->at, timeout);
+              adv_st(&adv->span, kRallySpan0);
+            }
+          } else if (adv_ld(&adv->key) == key) {
+            const int rest = p.timeout_thresh + 1 - timeout;
+            frames += rest;  // the counter at TIMEOUT_THRESH + 1: the end test below fires
+            timeout = p.timeout_thresh + 1;
+            if (lig == 0) adv->skipped += rest;
+          } else if (timeout - at >= adv_ld(&adv->span)) {
+            if (lig == 0) {
+              adv_st(&adv->key, key);
+              adv_st(&adv->at, timeout);
+              adv_st(&adv->span, 2 * adv_ld(&adv->span));
+            }
+          }
         }
       }
       if (st.s1 >= p.win_score || st.s2 >= p.win_score || st.done() || timeout > p.timeout_thresh) {
@@ -161,7 +264,16 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
   }
   if (p.counters) {
     if (lig == 0 && c_games) {
-      atomicAdd((unsigned long long *)&p.counters[0], (unsigned long long)c_steps);
+      if constexpr (kAdvance) {
+        // [0] the frames stepped one at a time: the episodes' frames minus those
+        // of periodic rallies jumped [8] and of serve delays advanced [12]
+        const uint32_t skipped = adv->skipped, hidden = adv->hidden;
+        atomicAdd((unsigned long long *)&p.counters[0], (unsigned long long)(c_steps - skipped - hidden));
+        if (skipped) atomicAdd((unsigned long long *)&p.counters[8], (unsigned long long)skipped);
+        if (hidden) atomicAdd((unsigned long long *)&p.counters[12], (unsigned long long)hidden);
+      } else {
+        atomicAdd((unsigned long long *)&p.counters[0], (unsigned long long)c_steps);
+      }
       atomicAdd((unsigned long long *)&p.counters[3], (unsigned long long)c_games);
     }
     if (hl == 0 && c_fwd) {  // one lane per half-group: its network's forwards

@@ -50,7 +50,15 @@ struct ReluPolicy {
 template <int LN, int U, int O, typename WT>
 __global__ __launch_bounds__(256, O <= 3 ? 2 : 1) void k_relu(EvalParams p) {
   static_assert(2 * LN >= 8 && 2 * LN <= 32, "other_half / group_broadcast layouts");
-  cert_game<ReluPolicy<LN, U, O, WT>>(p);
+  cert_game<ReluPolicy<LN, U, O, WT>, false>(p);
+}
+
+// k_relu with the serve delays and periodic rallies advanced in closed form
+// (PG_KERNEL_ADVANCE, untraced launches; pg_certgame.hpp)
+template <int LN, int U, int O, typename WT>
+__global__ __launch_bounds__(256, O <= 3 ? 2 : 1) void k_relu_adv(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 32, "other_half / group_broadcast layouts");
+  cert_game<ReluPolicy<LN, U, O, WT>, true>(p);
 }
 
 template <int LN, int U, int O, typename WT>
@@ -75,7 +83,7 @@ bool relu_shape_ok(const pg_net &n) {
 
 static long relu_genes(int H, int O) { return (long)H * 7 + (long)O * (H + 1); }
 
-int32_t launch_relu(const EvalParams &p, int dtype, hipStream_t s) {
+int32_t launch_relu(const EvalParams &p, int dtype, bool advance, hipStream_t s) {
   const int H = p.nodes[1], O = p.nodes[2];
   if (p.n_nodes != 3 || p.nodes[0] != 6 || H < 1 || H > kReluMaxH || O < 2 || O > 4 || !p.bias)
     return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
@@ -86,7 +94,9 @@ int32_t launch_relu(const EvalParams &p, int dtype, hipStream_t s) {
     return fail(PG_ERR_INVALID, "relu kernel: a row stride is below the gene count");
   const int grid = cert_game_grid(p, LN);
   if (grid <= 0) return PG_OK;
-  PG_RELU_DISPATCH(k_relu, LN, O, dtype == PG_F64, grid, s, p);
+  // a traced launch records every frame: it runs with the advance off
+  if (advance && !p.trace) PG_RELU_DISPATCH(k_relu_adv, LN, O, dtype == PG_F64, grid, s, p);
+  else PG_RELU_DISPATCH(k_relu, LN, O, dtype == PG_F64, grid, s, p);
   PG_HIP(hipGetLastError());
   return PG_OK;
 }

@@ -26,7 +26,15 @@ namespace pg {
 template <int LN, int U1, int U2, int O, typename WT>
 __global__ __launch_bounds__(256, 2) void k_relu2(EvalParams p) {
   static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
-  cert_game<Relu2Policy<LN, U1, U2, O, WT>>(p);
+  cert_game<Relu2Policy<LN, U1, U2, O, WT>, false>(p);
+}
+
+// k_relu2 with the serve delays and periodic rallies advanced in closed form
+// (PG_KERNEL_ADVANCE, untraced launches; pg_certgame.hpp)
+template <int LN, int U1, int U2, int O, typename WT>
+__global__ __launch_bounds__(256, 2) void k_relu2_adv(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
+  cert_game<Relu2Policy<LN, U1, U2, O, WT>, true>(p);
 }
 
 template <int LN, int U1, int U2, int O, typename WT>
@@ -58,15 +66,18 @@ struct Relu2Family {
     return fail(PG_ERR_UNSUPPORTED, "pg_relu2_decide: the relu2 kernel's shapes [6, 2..64, 2..64, 2..4] with bias only");
   }
   static int32_t decide_no_bias() { return decide_bad_shape(); }
-  static void game(int LN, int O, bool f64, int grid, hipStream_t s, const EvalParams &p) {
-    PG_HIDDEN2_DISPATCH(k_relu2, LN, O, f64, grid, s, p);
+  static void game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p) {
+    if (advance) PG_HIDDEN2_DISPATCH(k_relu2_adv, LN, O, f64, grid, s, p);
+    else PG_HIDDEN2_DISPATCH(k_relu2, LN, O, f64, grid, s, p);
   }
   static void decide(int LN, int O, bool f64, int grid, hipStream_t s, const CertDecideParams &p) {
     PG_HIDDEN2_DISPATCH(k_relu2_decide, LN, O, f64, grid, s, p);
   }
 };
 
-int32_t launch_relu2(const EvalParams &p, int dtype, hipStream_t s) { return hidden2_launch<Relu2Family>(p, dtype, s); }
+int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, hipStream_t s) {
+  return hidden2_launch<Relu2Family>(p, dtype, advance, s);
+}
 
 }  // namespace pg
 

@@ -727,8 +727,10 @@ static size_t eval_base_workspace(const pg_eval_args *a) {
 }
 
 // the kernel pg_eval_population runs for a (PG_KERNEL_AUTO resolved)
+// (the low byte of pg_eval_args.kernel: PG_KERNEL_ADVANCE changes no choice and no workspace)
 static int resolve_kernel(const pg_eval_args *a) {
-  if (a->kernel != PG_KERNEL_AUTO) return a->kernel;
+  const int named = a->kernel & 0xff;
+  if (named != PG_KERNEL_AUTO) return named;
   if (a->net.activation == PG_ACT_RELU) {  // k_relu's or k_relu2's scope, else the general kernel (never SPLIT or WIDE)
     if (a->precision != PG_PREC_CERTIFIED) return PG_KERNEL_GENERAL;
     return relu_shape_ok(a->net) ? PG_KERNEL_RELU : (relu2_shape_ok(a->net) ? PG_KERNEL_RELU2 : PG_KERNEL_GENERAL);
@@ -787,6 +789,21 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   if (a->timeout_thresh != 0 && (a->timeout_thresh < 32 || a->timeout_thresh > (1 << 20)))
     return fail(PG_ERR_INVALID, "timeout_thresh=%d not 0 or in [32, 1048576]", a->timeout_thresh);
   if (a->win_score < 0) return fail(PG_ERR_INVALID, "win_score=%d < 0", a->win_score);
+  // pg_eval_args.kernel: a pg_kernel in the low byte, modifier bits above it.  From here on a
+  // is the caller's struct with the pg_kernel alone, so every scope check and message below
+  // is the base kernel's
+  if (a->kernel & ~(0xff | PG_KERNEL_ADVANCE))
+    return fail(PG_ERR_INVALID, "kernel=0x%x: unknown bits above the pg_kernel (PG_KERNEL_ADVANCE = 0x100 only)",
+                (unsigned)a->kernel);
+  const bool advance = (a->kernel & PG_KERNEL_ADVANCE) != 0;
+  pg_eval_args named = *a;
+  named.kernel = a->kernel & 0xff;
+  a = &named;
+  if (advance && a->kernel != PG_KERNEL_AUTO && a->kernel != PG_KERNEL_RELU && a->kernel != PG_KERNEL_RELU2 &&
+      a->kernel != PG_KERNEL_SIG2)
+    return fail(PG_ERR_UNSUPPORTED,
+                "PG_KERNEL_ADVANCE: kernel=%d has no closed-form frame advance to switch on (the advance bit goes "
+                "with AUTO, RELU, RELU2 and SIG2; SPLIT and WIDE always advance)", a->kernel);
   if (a->kernel == PG_KERNEL_RELU2) {  // its scope is checked even for an empty launch
     if (a->net.activation != PG_ACT_RELU)
       return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu2 kernel evaluates PG_ACT_RELU networks only");
@@ -920,13 +937,13 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     if (!relu_shape_ok(a->net))
       return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
     if (a->precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "relu kernel is the certified-precision path");
-    rc = launch_relu(p, a->net.dtype, s);
+    rc = launch_relu(p, a->net.dtype, advance, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_RELU2) {  // (activation, shape and precision were checked on entry)
-    rc = launch_relu2(p, a->net.dtype, s);
+    rc = launch_relu2(p, a->net.dtype, advance, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_SIG2) {  // (the same)
-    rc = launch_sig2(p, a->net.dtype, s);
+    rc = launch_sig2(p, a->net.dtype, advance, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_GENERAL) {
     const size_t lds = 2 * (size_t)(p.max_width + 1) * sizeof(double);

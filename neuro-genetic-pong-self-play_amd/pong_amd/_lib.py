@@ -31,6 +31,7 @@ PG_KERNEL_RELU = 6
 PG_KERNEL_RELU2 = 7
 PG_KERNEL_RELU_WIDE = 8
 PG_KERNEL_SIG2 = 9
+PG_KERNEL_ADVANCE = 0x100  # modifier bit of pg_eval_args.kernel: closed-form frame advance on RELU, RELU2, SIG2
 PG_STATE_FIELDS = 16
 STATE_FIELD_NAMES = ("ball_x", "ball_y", "ball_vx", "ball_vy", "ball_visible", "serve_timer",
                      "serve_dir", "hits", "point", "lpy", "rpy", "score1", "score2",

@@ -19,6 +19,9 @@ PREPS = {"all": L.PG_PREP_ALL, "genomes": L.PG_PREP_GENOMES, "rest": L.PG_PREP_R
 KERNELS = {"auto": L.PG_KERNEL_AUTO, "general": L.PG_KERNEL_GENERAL, "split": L.PG_KERNEL_SPLIT,
            "wide": L.PG_KERNEL_WIDE, "relu": L.PG_KERNEL_RELU, "relu2": L.PG_KERNEL_RELU2,
            "relu_wide": L.PG_KERNEL_RELU_WIDE, "sig2": L.PG_KERNEL_SIG2}
+# "+advance" (PG_KERNEL_ADVANCE): the certified f32 families advance serve delays and periodic
+# rallies in closed form, with the same results; "auto+advance" where AUTO picks relu or relu2
+KERNELS.update({name + "+advance": KERNELS[name] | L.PG_KERNEL_ADVANCE for name in ("relu", "relu2", "sig2", "auto")})
 ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 

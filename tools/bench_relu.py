@@ -17,6 +17,11 @@ interquartile range) of >= 20 launches are reported.
         --runs relu_wide:4096 general:4096                                        # k_wide's ReLU instances (4.2e)
     python tools/bench_relu.py --shape 6 64 64 3 --activation sigmoid \
         --runs sig2:4096 general:4096 wide:4096                                   # k_sig2
+    python tools/bench_relu.py --runs relu:4096 relu+advance:4096 relu:4096 relu+advance:4096   # the closed-form
+        # frame advance against its base kernel, alternating; relu2+advance and sig2+advance alike
+
+Every run reports rally_share and serve_delay_share: counters [8] and [12] as
+shares of the episode frames (0 for a kernel that steps every frame).
 
 --activation sets the activation of the general and wide runs (default relu;
 relu, relu2 and relu_wide runs are always ReLU, sig2 and service runs always
@@ -58,9 +63,10 @@ def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64, g
 
 
 KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu_wide": "k_wide<relu>", "general": "k_general",
-                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide"}
+                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide",
+                "relu+advance": "k_relu_adv", "relu2+advance": "k_relu2_adv", "sig2+advance": "k_sig2_adv"}
 FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid",
-                    "wide": "sigmoid"}
+                    "wide": "sigmoid", "relu+advance": "relu", "relu2+advance": "relu", "sig2+advance": "sigmoid"}
 
 
 def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, activation="relu", genes="normal"):
@@ -94,9 +100,11 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
             "ms_iqr": round(float(q3 - q1), 4), "stepped_env_steps": int(c[0]), "episode_frames": frames,
             "stepped_env_steps_per_s": round(int(c[0]) / (med * 1e-3), 1), "forwards": int(c[1]),
             "f64_forwards": int(c[2]), "f64_share": round(int(c[2]) / max(int(c[1]), 1), 6),
+            # the episode frames not stepped one at a time: periodic rallies jumped [8], serve delays advanced [12]
+            "rally_share": round(int(c[8]) / max(frames, 1), 6), "serve_delay_share": round(int(c[12]) / max(frames, 1), 6),
             "genes": "U[0,1)" if genes == "uniform" else "N(0,3)",
             "device": torch.cuda.get_device_name(dev)}
-    if name == "sig2":  # the cascade: forwards the f32 certificate left undecided (counter [4])
+    if name.startswith("sig2"):  # the cascade: forwards the f32 certificate left undecided (counter [4])
         out["stage1_failures"] = int(c[4])
         out["stage1_failure_share"] = round(int(c[4]) / max(int(c[1]), 1), 6)
     if name == "relu_wide":  # each network pass streams one network's genes once
@@ -110,7 +118,8 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service")
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service, "
+                   "relu+advance, relu2+advance, sig2+advance")
     p.add_argument("--shape", nargs="+", type=int, default=SHAPE,
                    help="NETWORK_SHAPE (default 6 64 3; relu2 needs two hidden layers, e.g. 6 64 64 3)")
     p.add_argument("--warmup", type=int, default=3)
