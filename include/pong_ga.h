@@ -165,7 +165,22 @@ enum {
                                on, where it picks SPLIT, WIDE or GENERAL the bit changes nothing.  Every other
                                explicit kernel with the bit: PG_ERR_UNSUPPORTED (checked, like the bits, even
                                for an empty launch).  A launch with trace != NULL records every frame and so
-                               runs with the advance off, which is not an error ([8] = [12] = 0) */
+                               runs with the advance off, which is not an error ([8] = [12] = 0) */,
+  PG_KERNEL_SOLO = 0x800    /* scripted-opponent games on half a lane group, opt-in: PG_KERNEL_RELU,
+                               PG_KERNEL_RELU2 and PG_KERNEL_SIG2 give every game a group of 2 LN lanes, of which
+                               the left paddle's half idles against PG_OPP_HARDCODED, PG_OPP_ROM_CPU and
+                               PG_OPP_SCORE.  With this bit OR-ed in such a game is played by one half-group alone
+                               and only a PG_OPP_NN game takes a whole group -- every output and all 16 counters
+                               bit for bit the base kernel's.  (0x800 because 0x200, 0x400 and 0x10000 are pinned
+                               as PG_ERR_INVALID by the advance bit's tests.)  The rules are PG_KERNEL_ADVANCE's:
+                               the scope, the refusals and their messages are the base kernel's, the workspace is
+                               the same (the second game counter lives in its 256-byte header); PG_KERNEL_AUTO
+                               with the bit resolves exactly as without it, solo where it picks RELU or RELU2,
+                               no change where it picks SPLIT, WIDE or GENERAL; every other explicit kernel with
+                               the bit: PG_ERR_UNSUPPORTED (after the advance bit's refusal when both are set;
+                               checked even for an empty launch).  The two bits combine freely.  A traced launch
+                               keeps solo on (it steps every frame); with both bits it runs the solo kernel
+                               without the advance */
 };
 
 /* pg_eval_args.prep: the SPLIT kernel's lane records (one per network of the
@@ -235,7 +250,7 @@ typedef struct pg_eval_args {
   uint8_t *trace;                /* optional [trace_games, trace_cap] per-frame action codes */
   int32_t trace_games;           /* games (genome-major index g = i*n_games + game) traced */
   int32_t trace_cap;
-  int32_t kernel;                /* pg_kernel, optionally | PG_KERNEL_ADVANCE */
+  int32_t kernel;                /* pg_kernel, optionally | PG_KERNEL_ADVANCE | PG_KERNEL_SOLO */
   int32_t group_lanes;           /* lanes per game of RESIDENT (4..64) / SPLIT (8..64), 0 = auto */
   void *workspace;               /* device scratch of pg_eval_workspace_bytes() bytes */
   size_t workspace_bytes;

@@ -81,6 +81,10 @@ ACTIVATION = "sigmoid"
 # the certified f32 kernels (serve delays and periodic rallies are not stepped
 # frame by frame; the same results); "auto+advance" picks as
 # "auto" does and advances where that is the relu or the relu2 kernel.
+# "+solo" on the same four names ("relu+solo", "relu2+solo", "sig2+solo",
+# "auto+solo"; with the advance "auto+advance+solo", in either order) plays the
+# games against the scripted opponents -- evaluate()'s first three, and all of
+# generation 0 -- on half a lane group each (the same results).
 KERNEL = "auto"
 # Storage type of genomes on the device; float64 keeps Python floats exact.
 GENOME_DTYPE = "float64"

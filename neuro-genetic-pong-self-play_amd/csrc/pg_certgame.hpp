@@ -1,9 +1,10 @@
 // pg_certgame.hpp -- what the certified f32 kernel families share: k_relu
 // (pg_relu.hip), k_relu2 (pg_relu2.hip) and k_sig2 (pg_sig2.hip) are thin
-// __global__ wrappers of the one game loop cert_game<P, kAdvance>, and
+// __global__ wrappers of the one game loop cert_game<P, kAdvance, kSolo>, and
 // k_relu_decide, k_relu2_decide and k_sig2_decide of the one pass
 // cert_decide_pass<P>.  k_relu_adv, k_relu2_adv and k_sig2_adv wrap the same
-// loop with kAdvance on (PG_KERNEL_ADVANCE).  DESIGN.md 4.2g, 4.2h.
+// loop with kAdvance on (PG_KERNEL_ADVANCE), k_*_solo and k_*_adv_solo with
+// kSolo on (PG_KERNEL_SOLO).  DESIGN.md 4.2g, 4.2h, 4.2i.
 //
 // A policy P describes one instance of a family to both bodies:
 //   LN, O, WT        lanes per network (a half-group), outputs, genome type
@@ -50,9 +51,10 @@ struct CertDecideParams {
   int n, H1, H2;
 };
 
-// kAdvance's per-group record: Brent's saved rally key, the no-score count it
-// was saved at (-1: no search open) and the span; the group's frames advanced
-// in closed form.  In LDS, written by the group's lane 0 and read only behind
+// kAdvance's per-group record (with kSolo: per half-group): Brent's saved rally
+// key, the no-score count it was saved at (-1: no search open) and the span; the
+// group's frames advanced in closed form.  In LDS, written by the group's lane 0
+// (with kSolo: the half-group's, the counts by the game's first lane) and read only behind
 // the rare tests (a bounce past the kRallyHits-th return, a serve, the end), so
 // the common frame path holds none of it in registers.  The search's three
 // fields go through relaxed atomics (adv_ld / adv_st): the other lanes of the
@@ -75,6 +77,17 @@ __device__ __forceinline__ CertAdvance *cert_advance_lds() {
   return adv;
 }
 
+// kSolo: the next game of one of the two queues -- the kOppNN games (kNN) or the
+// others -- from its counter q, which walks all games; games_total: none is left
+template <bool kNN>
+__device__ __forceinline__ int cert_take(const EvalParams &p, unsigned int *q, int games_total) {
+  for (;;) {
+    const unsigned int w = atomicAdd(q, 1u);
+    if (w >= (unsigned int)games_total) return games_total;
+    if ((p.kind[w] == kOppNN) == kNN) return (int)w;
+  }
+}
+
 // evaluate() (main.py:28-66): an aligned group of 2 LN lanes plays one game to
 // its end, taking games from the p.work queue; lanes [0, LN) hold the right
 // paddle's network (the genome), lanes [LN, 2 LN) the left paddle's (a
@@ -84,7 +97,20 @@ __device__ __forceinline__ CertAdvance *cert_advance_lds() {
 // only): then a serve delay's hidden-ball frames and the rest of a rally proven
 // periodic are advanced in closed form, k_service's rules (pg_service.hpp,
 // DESIGN.md 4.2h) -- the same results, counters [12] and [8].
-template <class P, bool kAdvance>
+//
+// kSolo (PG_KERNEL_SOLO, the k_*_solo wrappers): a game against
+// a scripted opponent or the ROM CPU has no left network, so a half-group plays
+// it alone -- role 0, the right paddle's unmirrored features, whichever half it
+// is -- and only a game against a hall-of-fame row takes the whole group (pair).
+// Two queues walk the games: p.work[0] hands out the kOppNN ones, p.work[1] the
+// others, each over all indices, the taking lane skipping the other queue's.  A
+// free group takes NN games while that queue lasts; from then on each half takes
+// solo games on its own.  Both halves of a pair game come free at the same
+// frame, so no half ever waits for its sibling: no barrier, no spin.  Every game
+// variable below is uniform over the lanes that play the game; the game's first
+// lane (lead) writes its results.  The per-game work is the base loop's, so the
+// outputs and all 16 counters are too.
+template <class P, bool kAdvance, bool kSolo = false>
 __device__ __forceinline__ void cert_game(const EvalParams &params) {
   // a copy of this function's own: its fields are values from here on.  Read
   // through the reference they stay loads of unknown memory until this body is
@@ -98,6 +124,11 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
   const int lig = threadIdx.x & (L - 1);
   const int half = lig / LN, hl = lig & (LN - 1);
   const int leader = lane & ~(L - 1);
+  // (below, the first lane of what keeps a kAdvance record and reports counters
+  // -- the group; kSolo: the half-group -- is spelled out as "kSolo ? hl == 0 :
+  // lig == 0" and a game's first lane as "kSolo ? lead : lig == 0" at each use:
+  // with either in a named bool, or took as a local of the loop body, the base
+  // kernels come out differently allocated and scheduled)
   typename P::Lds &lds = lds_all[threadIdx.x / LN];
   const WT *genomes = (const WT *)p.genomes;
   const WT *opponents = (const WT *)p.opponents;
@@ -106,16 +137,21 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
   // per lane: far below 2^32.  c_fail (stage > 0) is c_f64 itself where the
   // stages are 0/1: a counter of its own there costs the frame loop registers
   uint32_t c_steps = 0, c_fwd = 0, c_fail = 0, c_f64 = 0, c_games = 0;
-  [[maybe_unused]] CertAdvance *adv = nullptr;  // this group's record (kAdvance)
+  [[maybe_unused]] CertAdvance *adv = nullptr;  // this group's record (kAdvance); kSolo: this half-group's
   if constexpr (kAdvance) {
-    adv = cert_advance_lds<256 / L>() + threadIdx.x / L;
-    if (lig == 0) {
+    if constexpr (kSolo) adv = cert_advance_lds<HPB>() + threadIdx.x / LN;
+    else adv = cert_advance_lds<256 / L>() + threadIdx.x / L;
+    if (kSolo ? hl == 0 : lig == 0) {
       adv_st(&adv->at, -1);
       adv->skipped = adv->hidden = 0;
     }
   }
 
-  bool have = false, more = true;  // a game in play; the queue may hold more
+  bool have = false, more = true;  // a game in play; the queue may hold more (kSolo: the NN queue)
+  // kSolo: the solo queue may hold more; this game takes the whole group; w is
+  // a game taken this round; this lane is its game's first
+  [[maybe_unused]] bool more_solo = kSolo, pair = !kSolo, took = false;
+  [[maybe_unused]] bool lead = lig == 0;
   int w = 0, kind = 0;
   bool live = false;  // this half's network plays (the left half: only against a hall-of-fame row)
   const WT *g = genomes;
@@ -123,24 +159,48 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
   Pong st;
   int act_r = 0, act_l = 0, timeout = 0, total = 0, frames = 0;
   for (;;) {
-    if (!have && more) {
-      int ww = 0;
-      if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
-      w = group_broadcast<L>(ww, leader);
-      if (w < games_total) {
+    if constexpr (kSolo) {
+      took = false;
+      // a free group: the next NN game.  (have and more are uniform over the
+      // group while more is set: its solo games start only once it is not)
+      if (!have && more) {
+        int ww = 0;
+        if (lig == 0) ww = cert_take<true>(p, p.work, games_total);
+        w = __shfl(ww, leader, 64);
+        more = took = w < games_total;
+        pair = true;
+        lead = lig == 0;
+      }
+      // a free half-group, the NN queue exhausted: the next solo game
+      if (!have && !more && more_solo) {
+        int ww = 0;
+        if (hl == 0) ww = cert_take<false>(p, p.work + 1, games_total);
+        w = __shfl(ww, lane & ~(LN - 1), 64);
+        more_solo = took = w < games_total;
+        pair = false;
+        lead = hl == 0;
+      }
+    }
+    if (kSolo ? took : !have && more) {
+      if constexpr (!kSolo) {
+        int ww = 0;
+        if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
+        w = group_broadcast<L>(ww, leader);
+      }
+      if (kSolo || w < games_total) {
         const int i = w / p.n_games, gi = w % p.n_games;
         kind = p.kind[w];
         const WT *gr = genomes + (long)genome_row(p, i) * p.gstride;
         const WT *gl = (kind == kOppNN) ? opponents + (long)p.opp[w] * p.ostride : gr;
-        g = half ? gl : gr;
-        live = half == 0 || kind == kOppNN;
+        g = half ? gl : gr;  // (kSolo: a solo game's kind is not kOppNN, so both halves get gr)
+        live = kSolo || half == 0 || kind == kOppNN;
         P::load(net, g, dims, lds, hl);
         st.reset(game_seed(p.seed, gi), kind == kOppRomCpu);
         act_r = act_l = timeout = total = frames = 0;
         have = true;
         // groups reload games in place: the last game's search must not survive
         if constexpr (kAdvance) {
-          if (lig == 0) adv_st(&adv->at, -1);
+          if (kSolo ? hl == 0 : lig == 0) adv_st(&adv->at, -1);
         }
       } else {
         more = false;
@@ -169,7 +229,7 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
           // (main.py:128-135): after a start's 29 frames it stands at 28
           timeout += frames ? h : h - 1;
           frames += h;
-          if (lig == 0) adv->hidden += h;
+          if (kSolo ? lead : lig == 0) adv->hidden += h;
         }
       }
       const int s1b = st.s1, s2b = st.s2;
@@ -184,19 +244,22 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
         const int lbx2 = pvis ? pbx2 : bx2, lby2 = pvis ? pby2 : by2;
         // utils.inference's features (utils.py:139-153) as doubled centroids: the left
         // paddle sees the field mirrored, (160 - x) / 160 = (320 - 2x) / 320 exactly
+        // (kSolo: a half-group playing alone is the right paddle, whichever half it is)
+        int role = half;
+        if constexpr (kSolo) role = pair ? half : 0;
         int k[6];
-        k[0] = half ? 320 - bx2 : bx2;
+        k[0] = role ? 320 - bx2 : bx2;
         k[1] = by2;
-        k[2] = half ? 320 - lbx2 : lbx2;
+        k[2] = role ? 320 - lbx2 : lbx2;
         k[3] = lby2;
-        k[4] = half ? lc2 : rc2;
-        k[5] = half ? rc2 : lc2;
+        k[4] = role ? lc2 : rc2;
+        k[5] = role ? rc2 : lc2;
         float z[O];
         int stage;
         const int mine = index_to_code(P::decide(net, g, dims, k, live, lds, hl, z, stage));
-        const int other = other_half<L>(mine);
-        right = half ? other : mine;
-        left = half ? mine : other;
+        const int other = other_half<L>(mine);  // (kSolo: used in a pair game only; a solo game's left is set below)
+        right = role ? other : mine;
+        left = role ? mine : other;
         c_fwd += live ? 1 : 0;
         if constexpr (P::kF64Stage != 1) c_fail += stage > 0 ? 1 : 0;
         c_f64 += stage == P::kF64Stage ? 1 : 0;
@@ -208,7 +271,7 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
       act_l = clamp_action(lc2, left);
       act_r = clamp_action(rc2, right);
       if constexpr (!kAdvance) {  // (a traced launch runs the stepping kernel)
-        if (p.trace && w < p.trace_games && frames <= p.trace_cap && lig == 0)
+        if (p.trace && w < p.trace_games && frames <= p.trace_cap && (kSolo ? lead : lig == 0))
           p.trace[(long)w * p.trace_cap + frames - 1] = (uint8_t)(act_r | (act_l << 2) | (vis << 4));
       }
       if (frames > 1) {  // calculate_timeout_and_frames main.py:128-135
@@ -218,7 +281,7 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
           total += timeout;
           timeout = 0;
           if constexpr (kAdvance) {
-            if (lig == 0) adv_st(&adv->at, -1);  // a point: the next rally searches afresh
+            if (kSolo ? hl == 0 : lig == 0) adv_st(&adv->at, -1);  // a point: the next rally searches afresh
           }
         }
       }
@@ -235,7 +298,7 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
           const uint64_t key = rally_key(st, act_r, act_l);
           const int at = adv_ld(&adv->at);
           if (at < 0 || at > timeout) {
-            if (lig == 0) {
+            if (kSolo ? hl == 0 : lig == 0) {
               adv_st(&adv->key, key);
               adv_st(&adv->at, timeout);
               adv_st(&adv->span, kRallySpan0);
@@ -244,9 +307,9 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
             const int rest = p.timeout_thresh + 1 - timeout;
             frames += rest;  // the counter at TIMEOUT_THRESH + 1: the end test below fires
             timeout = p.timeout_thresh + 1;
-            if (lig == 0) adv->skipped += rest;
+            if (kSolo ? lead : lig == 0) adv->skipped += rest;
           } else if (timeout - at >= adv_ld(&adv->span)) {
-            if (lig == 0) {
+            if (kSolo ? hl == 0 : lig == 0) {
               adv_st(&adv->key, key);
               adv_st(&adv->at, timeout);
               adv_st(&adv->span, 2 * adv_ld(&adv->span));
@@ -255,15 +318,20 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
         }
       }
       if (st.s1 >= p.win_score || st.s2 >= p.win_score || st.done() || timeout > p.timeout_thresh) {
-        c_steps += frames;
-        c_games += 1;
-        if (lig == 0) finish_game(p, w, st, frames, total);
+        if constexpr (kSolo) {  // (counted by the game's first lane alone: half-group leaders report)
+          c_steps += lead ? frames : 0;
+          c_games += lead ? 1 : 0;
+        } else {
+          c_steps += frames;
+          c_games += 1;
+        }
+        if (kSolo ? lead : lig == 0) finish_game(p, w, st, frames, total);
         have = false;
       }
     }
   }
   if (p.counters) {
-    if (lig == 0 && c_games) {
+    if ((kSolo ? hl == 0 : lig == 0) && c_games) {
       if constexpr (kAdvance) {
         // [0] the frames stepped one at a time: the episodes' frames minus those
         // of periodic rallies jumped [8] and of serve delays advanced [12]

@@ -156,18 +156,25 @@ int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s
 // [6, H <= 256, 2..4] ReLU networks with bias on k_relu (pg_relu.hip): the
 // shapes it holds, and its launch (certified precision; no workspace beyond the base)
 bool relu_shape_ok(const pg_net &n);
-// advance (PG_KERNEL_ADVANCE): the k_*_adv instances, unless the launch is traced
-int32_t launch_relu(const EvalParams &p, int dtype, bool advance, hipStream_t s);
+// advance (PG_KERNEL_ADVANCE): the k_*_adv instances, unless the launch is traced;
+// solo (PG_KERNEL_SOLO): the k_*_solo instances, traced or not
+int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
 // [6, 2..64, 2..64, 2..4] ReLU networks with bias on k_relu2 (pg_relu2.hip; the
 // host side it shares with k_sig2 is pg_hidden2.hpp's): the same for two hidden layers
 bool relu2_shape_ok(const pg_net &n);
-int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, hipStream_t s);
+int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
 // [6, 2..64, 2..64, 2..4] sigmoid networks with bias on k_sig2 (pg_sig2.hip,
 // pg_hidden2.hpp): the shapes it holds (the bias is checked apart: its refusal
 // has its own message), and its launch (certified precision; no workspace beyond the base)
 bool sig2_shape_ok(const pg_net &n);
-int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, hipStream_t s);
+int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
+
+// the launches of the k_*_solo / k_*_adv_solo instances (PG_KERNEL_SOLO): each
+// family's source compiled again as a unit of its own (-DPG_SOLO_UNIT)
+void relu_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
+void relu2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
+void sig2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 
 }  // namespace pg

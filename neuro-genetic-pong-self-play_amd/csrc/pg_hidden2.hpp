@@ -439,7 +439,7 @@ inline bool hidden2_shape_ok(int n_nodes, const int32_t *nodes) {
 inline long hidden2_genes(int H1, int H2, int O) { return (long)H1 * 7 + (long)H2 * (H1 + 1) + (long)O * (H2 + 1); }
 
 template <class F>
-int32_t hidden2_launch(const EvalParams &p, int dtype, bool advance, hipStream_t s) {
+int32_t hidden2_launch(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
   const int H1 = p.nodes[1], H2 = p.nodes[2], O = p.nodes[3];
   if (!hidden2_shape_ok(p.n_nodes, p.nodes)) return F::bad_shape();
   if (!p.bias) return F::no_bias();
@@ -450,7 +450,7 @@ int32_t hidden2_launch(const EvalParams &p, int dtype, bool advance, hipStream_t
   const int grid = cert_game_grid(p, LN);
   if (grid <= 0) return PG_OK;
   // a traced launch records every frame: it runs with the advance off
-  F::game(LN, O, dtype == PG_F64, advance && !p.trace, grid, s, p);
+  F::game(LN, O, dtype == PG_F64, advance && !p.trace, solo, grid, s, p);
   PG_HIP(hipGetLastError());
   return PG_OK;
 }

@@ -16,7 +16,9 @@
 //                         from the genes.  Every frame is stepped.
 // The game loop and the decide pass are the certified families' shared ones
 // (pg_certgame.hpp); this file holds k_relu's policy and its host side.
-// DESIGN.md 4.2c, 4.2g.
+// Compiled a second time with -DPG_SOLO_UNIT (pong_amd/build.py) it holds
+// k_relu_solo and k_relu_adv_solo (PG_KERNEL_SOLO) and nothing else, so this
+// unit's kernels are what they were without them.  DESIGN.md 4.2c, 4.2g, 4.2i.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pong_ga.h"
@@ -47,6 +49,36 @@ struct ReluPolicy {
   }
 };
 
+// the instances: LN = relu_lanes(H) lanes per network, kReluUnits units per lane
+#define PG_RELU_DISPATCH(KERNEL, LN, O, f64, grid, s, p)                            \
+  do {                                                                              \
+    if (LN == 4) PG_CERT_DISPATCH(KERNEL, 4, (kReluUnits), O, f64, grid, s, p);     \
+    else if (LN == 8) PG_CERT_DISPATCH(KERNEL, 8, (kReluUnits), O, f64, grid, s, p); \
+    else PG_CERT_DISPATCH(KERNEL, 16, (kReluUnits), O, f64, grid, s, p);            \
+  } while (0)
+
+#ifdef PG_SOLO_UNIT
+// k_relu and k_relu_adv with a half-group per game against a scripted opponent
+// (PG_KERNEL_SOLO; pg_certgame.hpp)
+template <int LN, int U, int O, typename WT>
+__global__ __launch_bounds__(256, O <= 3 ? 2 : 1) void k_relu_solo(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 32, "other_half / group_broadcast layouts");
+  cert_game<ReluPolicy<LN, U, O, WT>, false, true>(p);
+}
+
+template <int LN, int U, int O, typename WT>
+__global__ __launch_bounds__(256, O <= 3 ? 2 : 1) void k_relu_adv_solo(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 32, "other_half / group_broadcast layouts");
+  cert_game<ReluPolicy<LN, U, O, WT>, true, true>(p);
+}
+
+void relu_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p) {
+  if (advance) PG_RELU_DISPATCH(k_relu_adv_solo, LN, O, f64, grid, s, p);
+  else PG_RELU_DISPATCH(k_relu_solo, LN, O, f64, grid, s, p);
+}
+
+}  // namespace pg
+#else
 template <int LN, int U, int O, typename WT>
 __global__ __launch_bounds__(256, O <= 3 ? 2 : 1) void k_relu(EvalParams p) {
   static_assert(2 * LN >= 8 && 2 * LN <= 32, "other_half / group_broadcast layouts");
@@ -73,17 +105,9 @@ bool relu_shape_ok(const pg_net &n) {
          n.nodes[2] <= 4 && n.bias != 0;
 }
 
-// the instances: LN = relu_lanes(H) lanes per network, kReluUnits units per lane
-#define PG_RELU_DISPATCH(KERNEL, LN, O, f64, grid, s, p)                            \
-  do {                                                                              \
-    if (LN == 4) PG_CERT_DISPATCH(KERNEL, 4, (kReluUnits), O, f64, grid, s, p);     \
-    else if (LN == 8) PG_CERT_DISPATCH(KERNEL, 8, (kReluUnits), O, f64, grid, s, p); \
-    else PG_CERT_DISPATCH(KERNEL, 16, (kReluUnits), O, f64, grid, s, p);            \
-  } while (0)
-
 static long relu_genes(int H, int O) { return (long)H * 7 + (long)O * (H + 1); }
 
-int32_t launch_relu(const EvalParams &p, int dtype, bool advance, hipStream_t s) {
+int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
   const int H = p.nodes[1], O = p.nodes[2];
   if (p.n_nodes != 3 || p.nodes[0] != 6 || H < 1 || H > kReluMaxH || O < 2 || O > 4 || !p.bias)
     return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
@@ -95,7 +119,8 @@ int32_t launch_relu(const EvalParams &p, int dtype, bool advance, hipStream_t s)
   const int grid = cert_game_grid(p, LN);
   if (grid <= 0) return PG_OK;
   // a traced launch records every frame: it runs with the advance off
-  if (advance && !p.trace) PG_RELU_DISPATCH(k_relu_adv, LN, O, dtype == PG_F64, grid, s, p);
+  if (solo) relu_solo_game(LN, O, dtype == PG_F64, advance && !p.trace, grid, s, p);
+  else if (advance && !p.trace) PG_RELU_DISPATCH(k_relu_adv, LN, O, dtype == PG_F64, grid, s, p);
   else PG_RELU_DISPATCH(k_relu, LN, O, dtype == PG_F64, grid, s, p);
   PG_HIP(hipGetLastError());
   return PG_OK;
@@ -128,3 +153,4 @@ extern "C" int32_t pg_relu_decide(const pg_relu_decide_args *a, void *stream) {
   PG_HIP(hipGetLastError());
   return PG_OK;
 }
+#endif  // PG_SOLO_UNIT

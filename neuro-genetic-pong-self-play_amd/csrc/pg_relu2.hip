@@ -13,7 +13,10 @@
 //                         undecided half-groups the f64 forward in numpy's
 //                         order from the genes.
 // This file holds the family's kernels, its messages and its C entry point; the
-// host side it shares with k_sig2 is pg_hidden2.hpp's.  DESIGN.md 4.2d, 4.2g.
+// host side it shares with k_sig2 is pg_hidden2.hpp's.  Compiled a second time
+// with -DPG_SOLO_UNIT (pong_amd/build.py) it holds k_relu2_solo and
+// k_relu2_adv_solo (PG_KERNEL_SOLO) and nothing else, so this unit's kernels
+// are what they were without them.  DESIGN.md 4.2d, 4.2g.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pong_ga.h"
@@ -23,6 +26,28 @@
 
 namespace pg {
 
+#ifdef PG_SOLO_UNIT
+// k_relu2 and k_relu2_adv with a half-group per game against a scripted opponent
+// (PG_KERNEL_SOLO; pg_certgame.hpp)
+template <int LN, int U1, int U2, int O, typename WT>
+__global__ __launch_bounds__(256, 2) void k_relu2_solo(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
+  cert_game<Relu2Policy<LN, U1, U2, O, WT>, false, true>(p);
+}
+
+template <int LN, int U1, int U2, int O, typename WT>
+__global__ __launch_bounds__(256, 2) void k_relu2_adv_solo(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
+  cert_game<Relu2Policy<LN, U1, U2, O, WT>, true, true>(p);
+}
+
+void relu2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p) {
+  if (advance) PG_HIDDEN2_DISPATCH(k_relu2_adv_solo, LN, O, f64, grid, s, p);
+  else PG_HIDDEN2_DISPATCH(k_relu2_solo, LN, O, f64, grid, s, p);
+}
+
+}  // namespace pg
+#else
 template <int LN, int U1, int U2, int O, typename WT>
 __global__ __launch_bounds__(256, 2) void k_relu2(EvalParams p) {
   static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
@@ -66,8 +91,9 @@ struct Relu2Family {
     return fail(PG_ERR_UNSUPPORTED, "pg_relu2_decide: the relu2 kernel's shapes [6, 2..64, 2..64, 2..4] with bias only");
   }
   static int32_t decide_no_bias() { return decide_bad_shape(); }
-  static void game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p) {
-    if (advance) PG_HIDDEN2_DISPATCH(k_relu2_adv, LN, O, f64, grid, s, p);
+  static void game(int LN, int O, bool f64, bool advance, bool solo, int grid, hipStream_t s, const EvalParams &p) {
+    if (solo) relu2_solo_game(LN, O, f64, advance, grid, s, p);
+    else if (advance) PG_HIDDEN2_DISPATCH(k_relu2_adv, LN, O, f64, grid, s, p);
     else PG_HIDDEN2_DISPATCH(k_relu2, LN, O, f64, grid, s, p);
   }
   static void decide(int LN, int O, bool f64, int grid, hipStream_t s, const CertDecideParams &p) {
@@ -75,8 +101,8 @@ struct Relu2Family {
   }
 };
 
-int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, hipStream_t s) {
-  return hidden2_launch<Relu2Family>(p, dtype, advance, s);
+int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
+  return hidden2_launch<Relu2Family>(p, dtype, advance, solo, s);
 }
 
 }  // namespace pg
@@ -84,3 +110,4 @@ int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, hipStream_t s
 extern "C" int32_t pg_relu2_decide(const pg_relu_decide_args *a, void *stream) {
   return pg::hidden2_decide<pg::Relu2Family>(a, stream);
 }
+#endif  // PG_SOLO_UNIT

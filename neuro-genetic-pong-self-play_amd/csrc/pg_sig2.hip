@@ -13,7 +13,10 @@
 //                         and then the f64 forward in numpy's order from the
 //                         genes.  No lane records, no workspace beyond the base.
 // This file holds the family's kernels, its messages and its C entry point; the
-// host side it shares with k_relu2 is pg_hidden2.hpp's.  DESIGN.md 4.2f, 4.2g.
+// host side it shares with k_relu2 is pg_hidden2.hpp's.  Compiled a second time
+// with -DPG_SOLO_UNIT (pong_amd/build.py) it holds k_sig2_solo and
+// k_sig2_adv_solo (PG_KERNEL_SOLO) and nothing else, so this unit's kernels
+// are what they were without them.  DESIGN.md 4.2f, 4.2g.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pong_ga.h"
@@ -23,6 +26,28 @@
 
 namespace pg {
 
+#ifdef PG_SOLO_UNIT
+// k_sig2 and k_sig2_adv with a half-group per game against a scripted opponent
+// (PG_KERNEL_SOLO; pg_certgame.hpp)
+template <int LN, int U1, int U2, int O, typename WT>
+__global__ __launch_bounds__(256, 2) void k_sig2_solo(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
+  cert_game<Sig2Policy<LN, U1, U2, O, WT>, false, true>(p);
+}
+
+template <int LN, int U1, int U2, int O, typename WT>
+__global__ __launch_bounds__(256, 2) void k_sig2_adv_solo(EvalParams p) {
+  static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
+  cert_game<Sig2Policy<LN, U1, U2, O, WT>, true, true>(p);
+}
+
+void sig2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p) {
+  if (advance) PG_HIDDEN2_DISPATCH(k_sig2_adv_solo, LN, O, f64, grid, s, p);
+  else PG_HIDDEN2_DISPATCH(k_sig2_solo, LN, O, f64, grid, s, p);
+}
+
+}  // namespace pg
+#else
 template <int LN, int U1, int U2, int O, typename WT>
 __global__ __launch_bounds__(256, 2) void k_sig2(EvalParams p) {
   static_assert(2 * LN >= 8 && 2 * LN <= 64, "other_half / group_broadcast layouts");
@@ -68,8 +93,9 @@ struct Sig2Family {
   static int32_t decide_no_bias() {
     return fail(PG_ERR_UNSUPPORTED, "pg_sig2_decide: the sig2 kernel needs a network with bias");
   }
-  static void game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p) {
-    if (advance) PG_HIDDEN2_DISPATCH(k_sig2_adv, LN, O, f64, grid, s, p);
+  static void game(int LN, int O, bool f64, bool advance, bool solo, int grid, hipStream_t s, const EvalParams &p) {
+    if (solo) sig2_solo_game(LN, O, f64, advance, grid, s, p);
+    else if (advance) PG_HIDDEN2_DISPATCH(k_sig2_adv, LN, O, f64, grid, s, p);
     else PG_HIDDEN2_DISPATCH(k_sig2, LN, O, f64, grid, s, p);
   }
   static void decide(int LN, int O, bool f64, int grid, hipStream_t s, const CertDecideParams &p) {
@@ -77,8 +103,8 @@ struct Sig2Family {
   }
 };
 
-int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, hipStream_t s) {
-  return hidden2_launch<Sig2Family>(p, dtype, advance, s);
+int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
+  return hidden2_launch<Sig2Family>(p, dtype, advance, solo, s);
 }
 
 }  // namespace pg
@@ -86,3 +112,4 @@ int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, hipStream_t s)
 extern "C" int32_t pg_sig2_decide(const pg_relu_decide_args *a, void *stream) {
   return pg::hidden2_decide<pg::Sig2Family>(a, stream);
 }
+#endif  // PG_SOLO_UNIT

@@ -719,7 +719,7 @@ int32_t pg_device_count(void) {
   return n;
 }
 
-// [0, 256): dynamic game counter; then one int32 per game (zero-division
+// [0, 256): dynamic game counters (PG_KERNEL_SOLO: two); then one int32 per game (zero-division
 // flags); for the staged kernel, then its prepared lane records
 static size_t eval_base_workspace(const pg_eval_args *a) {
   const size_t games = a ? (size_t)(a->n_genomes > 0 ? a->n_genomes : 0) * (size_t)(a->n_games > 0 ? a->n_games : 0) : 0;
@@ -727,7 +727,7 @@ static size_t eval_base_workspace(const pg_eval_args *a) {
 }
 
 // the kernel pg_eval_population runs for a (PG_KERNEL_AUTO resolved)
-// (the low byte of pg_eval_args.kernel: PG_KERNEL_ADVANCE changes no choice and no workspace)
+// (the low byte of pg_eval_args.kernel: PG_KERNEL_ADVANCE and PG_KERNEL_SOLO change no choice and no workspace)
 static int resolve_kernel(const pg_eval_args *a) {
   const int named = a->kernel & 0xff;
   if (named != PG_KERNEL_AUTO) return named;
@@ -792,10 +792,12 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
   // pg_eval_args.kernel: a pg_kernel in the low byte, modifier bits above it.  From here on a
   // is the caller's struct with the pg_kernel alone, so every scope check and message below
   // is the base kernel's
-  if (a->kernel & ~(0xff | PG_KERNEL_ADVANCE))
-    return fail(PG_ERR_INVALID, "kernel=0x%x: unknown bits above the pg_kernel (PG_KERNEL_ADVANCE = 0x100 only)",
+  if (a->kernel & ~(0xff | PG_KERNEL_ADVANCE | PG_KERNEL_SOLO))
+    return fail(PG_ERR_INVALID,
+                "kernel=0x%x: unknown bits above the pg_kernel (PG_KERNEL_ADVANCE = 0x100 and PG_KERNEL_SOLO = 0x800 only)",
                 (unsigned)a->kernel);
   const bool advance = (a->kernel & PG_KERNEL_ADVANCE) != 0;
+  const bool solo = (a->kernel & PG_KERNEL_SOLO) != 0;
   pg_eval_args named = *a;
   named.kernel = a->kernel & 0xff;
   a = &named;
@@ -804,6 +806,11 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     return fail(PG_ERR_UNSUPPORTED,
                 "PG_KERNEL_ADVANCE: kernel=%d has no closed-form frame advance to switch on (the advance bit goes "
                 "with AUTO, RELU, RELU2 and SIG2; SPLIT and WIDE always advance)", a->kernel);
+  if (solo && a->kernel != PG_KERNEL_AUTO && a->kernel != PG_KERNEL_RELU && a->kernel != PG_KERNEL_RELU2 &&
+      a->kernel != PG_KERNEL_SIG2)
+    return fail(PG_ERR_UNSUPPORTED,
+                "PG_KERNEL_SOLO: kernel=%d has no solo games on half a lane group to switch on (the solo bit goes "
+                "with AUTO, RELU, RELU2 and SIG2)", a->kernel);
   if (a->kernel == PG_KERNEL_RELU2) {  // its scope is checked even for an empty launch
     if (a->net.activation != PG_ACT_RELU)
       return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu2 kernel evaluates PG_ACT_RELU networks only");
@@ -937,13 +944,13 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     if (!relu_shape_ok(a->net))
       return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
     if (a->precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "relu kernel is the certified-precision path");
-    rc = launch_relu(p, a->net.dtype, advance, s);
+    rc = launch_relu(p, a->net.dtype, advance, solo, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_RELU2) {  // (activation, shape and precision were checked on entry)
-    rc = launch_relu2(p, a->net.dtype, advance, s);
+    rc = launch_relu2(p, a->net.dtype, advance, solo, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_SIG2) {  // (the same)
-    rc = launch_sig2(p, a->net.dtype, advance, s);
+    rc = launch_sig2(p, a->net.dtype, advance, solo, s);
     if (rc != PG_OK) return rc;
   } else if (kernel == PG_KERNEL_GENERAL) {
     const size_t lds = 2 * (size_t)(p.max_width + 1) * sizeof(double);

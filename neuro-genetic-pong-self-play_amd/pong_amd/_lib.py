@@ -32,6 +32,7 @@ PG_KERNEL_RELU2 = 7
 PG_KERNEL_RELU_WIDE = 8
 PG_KERNEL_SIG2 = 9
 PG_KERNEL_ADVANCE = 0x100  # modifier bit of pg_eval_args.kernel: closed-form frame advance on RELU, RELU2, SIG2
+PG_KERNEL_SOLO = 0x800  # modifier bit of pg_eval_args.kernel: scripted-opponent games on half a lane group (the same three)
 PG_STATE_FIELDS = 16
 STATE_FIELD_NAMES = ("ball_x", "ball_y", "ball_vx", "ball_vy", "ball_visible", "serve_timer",
                      "serve_dir", "hits", "point", "lpy", "rpy", "score1", "score2",

@@ -15,11 +15,15 @@ HEADERS = [os.path.join(CSRC, h) for h in ("pg_device.hpp", "pg_f64math.h", "pg_
 # one translation unit per kernel family, compiled in parallel and linked into one .so;
 # pg_service_more.hip is compiled once per (lanes per game, genome type): its ~100
 # k_service instantiations took 10 minutes as one unit
+# the certified families' sources are compiled twice: with -DPG_SOLO_UNIT a unit
+# holds only the family's k_*_solo instances (PG_KERNEL_SOLO), so the first
+# object's kernels stay what they were and the two compile side by side
 # (object name, source, extra flags)
 UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_wide", "pg_wide.hip", []), ("pg_pixels", "pg_pixels.hip", []),
          ("pg_hof", "pg_hof.hip", []), ("pg_gen", "pg_gen.hip", []), ("pg_decide", "pg_decide.hip", []),
          ("pg_relu", "pg_relu.hip", []), ("pg_relu2", "pg_relu2.hip", []),
-         ("pg_sig2", "pg_sig2.hip", [])] + [
+         ("pg_sig2", "pg_sig2.hip", []), ("pg_relu_solo", "pg_relu.hip", ["-DPG_SOLO_UNIT"]),
+         ("pg_relu2_solo", "pg_relu2.hip", ["-DPG_SOLO_UNIT"]), ("pg_sig2_solo", "pg_sig2.hip", ["-DPG_SOLO_UNIT"])] + [
     (f"pg_service_more_L{L}_{f}", "pg_service_more.hip",
      [f"-DPG_MORE_L={L}", f"-DPG_MORE_F64={f}"] + (["-DPG_MORE_DISPATCH"] if (L, f) == (8, 1) else []))
     for L in (8, 16, 32, 64) for f in (1, 0)]

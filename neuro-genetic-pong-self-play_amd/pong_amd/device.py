@@ -23,7 +23,26 @@ KERNELS = {"auto": L.PG_KERNEL_AUTO, "general": L.PG_KERNEL_GENERAL, "split": L.
 # rallies in closed form, with the same results; "auto+advance" where AUTO picks relu or relu2
 KERNELS.update({name + "+advance": KERNELS[name] | L.PG_KERNEL_ADVANCE for name in ("relu", "relu2", "sig2", "auto")})
 ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
+# the modifiers a kernel name may carry after "+" (kernel_code); "+solo" (PG_KERNEL_SOLO): the same
+# families play a game against a scripted opponent on half a lane group, with the same results
+MODIFIERS = {"advance": L.PG_KERNEL_ADVANCE, "solo": L.PG_KERNEL_SOLO}
+MODIFIED = ("relu", "relu2", "sig2", "auto")  # the bases either modifier goes with
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
+
+
+def kernel_code(name: str) -> int:
+    """pg_eval_args.kernel for a kernel name: a key of ``KERNELS`` without "+",
+    optionally followed by "+advance" and "+solo" in either order, each at most
+    once and only on relu, relu2, sig2 and auto (KeyError otherwise)."""
+    base, *mods = str(name).split("+")
+    ok = base in KERNELS and (not mods or base in MODIFIED) and len(set(mods)) == len(mods)
+    if not ok or any(m not in MODIFIERS for m in mods):
+        raise KeyError(f"kernel {name!r}: valid are {sorted(k for k in KERNELS if '+' not in k)}, and "
+                       f"{list(MODIFIED)} with '+advance' and/or '+solo' (e.g. 'auto+advance+solo')")
+    code = KERNELS[base]
+    for m in mods:
+        code |= MODIFIERS[m]
+    return code
 
 
 def gene_count(nodes, bias=True) -> int:
@@ -233,7 +252,7 @@ class Evaluator:
                              "n_active and row count on this evaluator")
         a.horizon = self.horizon if horizon is None else int(horizon)
         a.timeout_thresh, a.win_score = self.timeout_thresh, self.win_score
-        a.kernel = KERNELS[kernel or self.kernel]
+        a.kernel = kernel_code(kernel or self.kernel)
         a.group_lanes = self.group_lanes if group_lanes is None else int(group_lanes)
         ws = self._workspace(a)
         a.workspace, a.workspace_bytes = _ptr(ws), ws.numel()

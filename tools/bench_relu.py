@@ -19,6 +19,15 @@ interquartile range) of >= 20 launches are reported.
         --runs sig2:4096 general:4096 wide:4096                                   # k_sig2
     python tools/bench_relu.py --runs relu:4096 relu+advance:4096 relu:4096 relu+advance:4096   # the closed-form
         # frame advance against its base kernel, alternating; relu2+advance and sig2+advance alike
+    python tools/bench_relu.py --schedule reference --runs relu:4096 relu+solo:4096 relu:4096 relu+solo:4096
+        # scripted-opponent games on half a lane group against the base kernel; relu2+solo,
+        # sig2+solo and X+advance+solo against X+advance alike
+
+--schedule: selfplay (the default: every game against a hall member), reference
+(evaluate()'s kinds [0,1,2,3,3,3] per genome, the NN games against the same
+hall) or scripted (generation 0's [0,1,2,0,0,0]: no hall yet).  When the runs
+hold X and X+solo (or X+advance and X+advance+solo) at one population, their
+fitness, rewards, scores and frames on the timed inputs are asserted equal.
 
 Every run reports rally_share and serve_delay_share: counters [8] and [12] as
 shares of the episode frames (0 for a kernel that steps every frame).
@@ -63,19 +72,39 @@ def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64, g
 
 
 KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu_wide": "k_wide<relu>", "general": "k_general",
-                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide",
-                "relu+advance": "k_relu_adv", "relu2+advance": "k_relu2_adv", "sig2+advance": "k_sig2_adv"}
+                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide"}
 FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid",
-                    "wide": "sigmoid", "relu+advance": "relu", "relu2+advance": "relu", "sig2+advance": "sigmoid"}
+                    "wide": "sigmoid"}
+MODIFIED = ("relu", "relu2", "sig2")  # the families "+advance" and "+solo" go with (pong_amd.device.kernel_code)
+SCHEDULES = {"selfplay": None, "reference": [0, 1, 2, 3, 3, 3], "scripted": [0, 1, 2, 0, 0, 0]}
 
 
-def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, activation="relu", genes="normal"):
-    activation = FIXED_ACTIVATION.get(name, activation)
+def split_name(name):
+    """(base, modifiers) of a run's kernel name, e.g. "relu+advance+solo"; None if it is not one."""
+    base, *mods = name.split("+")
+    ok = base in KERNEL_NAMES and set(mods) <= {"advance", "solo"} and len(set(mods)) == len(mods)
+    return (base, frozenset(mods)) if ok and (not mods or base in MODIFIED) else None
+
+
+def schedule(ev, pop, hall, kinds):
+    """The launch's (kind, opp, mult): the self-play schedule's opponents under the per-genome kinds."""
+    kind, opp, mult = ev.selfplay_schedule(pop, hall.shape[0])
+    if kinds is not None:
+        kind = torch.tensor(kinds, dtype=torch.int32, device=kind.device).repeat(pop, 1)
+    return kind, opp, mult
+
+
+def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, activation="relu", genes="normal",
+        kinds=None, keep=None):
+    base, mods = split_name(name)
+    activation = FIXED_ACTIVATION.get(base, activation)
     kernel = "split" if name == "service" else name
     ev = Evaluator(shape, device=dev, dtype=dtype, activation=activation, kernel=kernel,
                    precision="f64" if name == "general" else "certified")
     genomes, hall = workload(pop, dev, shape=shape, dtype=dtype, genes=genes)
-    sched = ev.selfplay_schedule(pop, hall.shape[0])
+    sched = schedule(ev, pop, hall, kinds)
+    if kinds is not None and 3 not in kinds:
+        hall = None  # generation 0: no hall of fame yet
     res = None
     for _ in range(warmup):
         res, _ = ev.evaluate(genomes, *sched, opponents=hall, out=res, validate=False)
@@ -93,8 +122,11 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
     med = float(np.median(ms))
     q1, q3 = np.percentile(ms, [25, 75])
     frames = int(res.frames.sum())
-    out = {"kernel": KERNEL_NAMES[name], "genome_dtype": str(dtype).replace("torch.", ""),
-            "activation": activation, "shape": list(shape), "pop": pop, "games": 6, "hall": int(hall.shape[0]),
+    if keep is not None:  # the timed inputs' results, for the untimed X against X+solo comparison
+        keep[(base, mods, pop)] = [getattr(res, f).clone() for f in ("fitness", "rewards", "scores", "frames")]
+    kernel_name = KERNEL_NAMES[base] + ("_adv" if "advance" in mods else "") + ("_solo" if "solo" in mods else "")
+    out = {"kernel": kernel_name, "schedule": "selfplay" if kinds is None else kinds, "genome_dtype": str(dtype).replace("torch.", ""),
+            "activation": activation, "shape": list(shape), "pop": pop, "games": 6, "hall": int(hall.shape[0]) if hall is not None else 0,
             "launches": launches, "warmup": warmup,
             "ms_median": round(med, 4), "ms_min": round(float(ms.min()), 4), "ms_max": round(float(ms.max()), 4),
             "ms_iqr": round(float(q3 - q1), 4), "stepped_env_steps": int(c[0]), "episode_frames": frames,
@@ -119,7 +151,10 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service, "
-                   "relu+advance, relu2+advance, sig2+advance")
+                   "relu+advance, relu2+advance, sig2+advance, and relu, relu2, sig2 with +solo or +advance+solo")
+    p.add_argument("--schedule", default="selfplay", choices=sorted(SCHEDULES),
+                   help="the games' kinds per genome: selfplay (all against the hall), reference ([0,1,2,3,3,3]) or "
+                   "scripted (generation 0: [0,1,2,0,0,0], no hall)")
     p.add_argument("--shape", nargs="+", type=int, default=SHAPE,
                    help="NETWORK_SHAPE (default 6 64 3; relu2 needs two hidden layers, e.g. 6 64 64 3)")
     p.add_argument("--warmup", type=int, default=3)
@@ -132,12 +167,19 @@ def main():
     if args.launches < (5 if max(args.shape[1:-1]) > 256 else 20):
         p.error("--launches must be >= 20 (>= 5 for layers wider than 256: seconds per launch)")
     dev = torch.device("cuda", torch.cuda.current_device())
+    keep = {}
     for spec in args.runs:
         name, pop = spec.split(":")
-        if name not in KERNEL_NAMES:
+        if split_name(name) is None:
             p.error(f"unknown kernel {name!r}")
         print(json.dumps(run(name, int(pop), dev, args.warmup, args.launches, args.shape,
-                             getattr(torch, args.dtype), args.activation, args.genes)), flush=True)
+                             getattr(torch, args.dtype), args.activation, args.genes, SCHEDULES[args.schedule], keep)),
+              flush=True)
+    for (base, mods, pop), got in keep.items():  # X+solo against X, X+advance+solo against X+advance
+        if "solo" in mods:
+            want = keep.get((base, mods - {"solo"}, pop))
+            for a, b in zip(got, want or ()):
+                assert torch.equal(a, b), f"{base}+{'+'.join(sorted(mods))}:{pop} differs from its base kernel's results"
 
 
 if __name__ == "__main__":

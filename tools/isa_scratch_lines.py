@@ -6,7 +6,9 @@ kernel whose name contains SUBSTRING (default "_adv": the PG_KERNEL_ADVANCE
 instances) and reports, per kernel, its scratch_* instructions by the source
 line they belong to -- so that one can see that none sits on the frame's common
 path (cert_game's own lines in pg_certgame.hpp, Pong::step, the f32 chain and
-the certificate), DESIGN.md 4.2h.  Needs no GPU.
+the certificate), DESIGN.md 4.2h.  Each unit is built twice, the second time
+with -DPG_SOLO_UNIT as pong_amd/build.py does, so "_solo" lists the
+PG_KERNEL_SOLO instances.  Needs no GPU.
 
     python tools/isa_scratch_lines.py [SUBSTRING] > listing.txt
 """
@@ -21,12 +23,12 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "neuro-genetic-pong-self-play_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-UNITS = ("pg_relu.hip", "pg_relu2.hip", "pg_sig2.hip")
+UNITS = [(u, f) for u in ("pg_relu.hip", "pg_relu2.hip", "pg_sig2.hip") for f in ((), ("-DPG_SOLO_UNIT",))]
 
 
-def listing(tmp, unit):
+def listing(tmp, unit, flags):
     obj = os.path.join(tmp, unit + ".o")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
+    subprocess.check_call([HIPCC, *flags, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                            "-fno-slp-vectorize", "-I", os.path.join(REPO, "include"), "-gline-tables-only",
                            "--cuda-device-only", "--no-gpu-bundle-output", "-c", "-o", obj, os.path.join(CSRC, unit)])
     return subprocess.check_output([OBJDUMP, "-d", "-l", "--no-show-raw-insn", obj], text=True)
@@ -36,9 +38,9 @@ def main(argv):
     want = argv[0] if argv else "_adv"
     total = collections.Counter()
     with tempfile.TemporaryDirectory() as tmp:
-        for unit in UNITS:
+        for unit, flags in UNITS:
             sym, cur, rows = None, "?", {}
-            for ln in listing(tmp, unit).splitlines():
+            for ln in listing(tmp, unit, flags).splitlines():
                 m = re.match(r"^[0-9a-f]+ <(.+)>:$", ln)
                 if m:
                     sym = m.group(1)
