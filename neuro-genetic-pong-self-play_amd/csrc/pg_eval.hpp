@@ -1,6 +1,20 @@
 // pg_eval.hpp -- what the evaluation kernels of libpong_ga.so share across
-// translation units (pong_ga.hip: the small-network kernels and the C-ABI;
-// pg_wide.hip: the streaming kernel for wide two-hidden-layer networks).
+// translation units: EvalParams and the per-game helpers, and each unit's
+// host interface to pg_eval_population.
+//
+//   pong_ga.hip          the C-ABI of the evaluation (pg_eval_population, pg_decide,
+//                        pg_wide_decide), errors, k_fitness, k_service's bench instance
+//                        and the kernels its generated code depends on
+//                        (k_forward_resident, k_physics_* with pg_physics_*)
+//   pg_service_more.hip  every other k_service instance
+//   pg_general.hip       the f64 path: k_general, pg_forward with k_forward_general
+//   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
+//   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
+//   pg_decide.hip        k_decide (pg_decide)
+//   pg_ga.hip            selection, variation, schedule, row gather and hash
+//   pg_gen.hip, pg_hof.hip, pg_pixels.hip    the generation's device steps, the
+//                        hall of fame on the device, frames as pixels
+//   pg_hof_scan.cpp      the hall-of-fame scans on the host (plain C++)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,18 +22,9 @@
 
 #include "../../include/pong_ga.h"
 #include "pg_device.hpp"
+#include "pg_fail.hpp"
 
 namespace pg {
-
-// Record a failure for pg_last_error() and return code (defined in pong_ga.hip).
-int32_t fail(int32_t code, const char *fmt, ...);
-
-#define PG_HIP(call)                                                                  \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess)                                                             \
-      return fail(PG_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_));        \
-  } while (0)
 
 // ------------------------------------------------------- kernel params ----
 struct EvalParams {
@@ -114,7 +119,22 @@ __device__ inline double feat64(int k) { return __dmul_rn(0.5, (double)k) / 160.
 __device__ inline double feat64_flip(int k) { return (160.0 - __dmul_rn(0.5, (double)k)) / 160.0; }
 
 
+// ---------------------------------------------- host side (pong_ga.hip) ----
 int num_cus();
+int32_t check_net(const pg_net &n, bool game);  // game: the game's 6 inputs required
+int gene_count(const pg_net &n);                // -1: above 2^31 - 1
+int max_width(const pg_net &n);
+inline size_t align256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// the network's fields of a kernel's parameters (EvalParams, pg_general.hip's FwdParams)
+template <class Params>
+inline void set_net(Params &p, const pg_net &n) {
+  for (int i = 0; i < n.n_nodes; ++i) p.nodes[i] = n.nodes[i];
+  p.n_nodes = n.n_nodes;
+  p.bias = n.bias ? 1 : 0;
+  p.max_width = max_width(n);
+  p.activation = n.activation;
+}
 
 // Append one hard-decision record (pg_eval_args.hard_log); counters[9] counts them all.
 __device__ inline void log_hard_raw(uint32_t *hard_log, uint64_t *counters, int hard_cap, int row, int is_opp, int idx,
@@ -146,16 +166,51 @@ struct DecideParams {
 // pong_ga.hip uses for k_service crashes the register allocator on k_decide)
 int32_t launch_decide(const DecideParams &p, int L, int O, bool f64, size_t lds, hipStream_t s);
 
-// [6, H1, H2, O] networks (two hidden layers, H1, H2 <= 512, O in 2..4,
-// n_games <= 8) on the weight-streaming kernel k_wide (pg_wide.hip); launch_wide
-// runs the sigmoid or the ReLU instance (PG_KERNEL_RELU_WIDE) by p.activation.
+// ------------------------------------------------- the kernel families ----
+// Each family's unit exports its scope and its launch.  X_scope(a) is the
+// refusal, in the family's words, of a network or of arguments that the kernel
+// does not evaluate (activation first, then shape, bias, precision, horizon,
+// hard-case log, as far as the family has a rule of its own), or PG_OK.  It is
+// the only place that states them: the launches take what pg_eval_population
+// let through.  a.kernel is the pg_kernel alone, without modifier bits.
+
+// the f64 kernel for any NETWORK_SHAPE (k_general, pg_general.hip)
+int32_t launch_general(const EvalParams &p, int dtype, hipStream_t s);
+
+// pg_forward's parameters (pg_general.hip) and its certified path for the split
+// kernel's shapes, k_forward_resident (pong_ga.hip, which says why there)
+struct FwdParams {
+  const void *genomes;
+  const int32_t *gidx;
+  const double *x;
+  int32_t *index;
+  double *act;
+  double *z_all, *h_all;  // optional [n, sum(nodes[1:])]: every layer's pre-activations / activations
+  uint64_t *counters;
+  int64_t gstride;
+  int n;
+  int nodes[PG_MAX_NODES];
+  int n_nodes, bias, max_width, n_units, activation;
+};
+int32_t launch_forward_resident(const FwdParams &p, int dtype, hipStream_t s);
+
+// [6, H <= 256, 2..4] sigmoid networks on k_service (SPLIT; pong_ga.hip, pg_service_more.hip)
+bool resident_shape_ok(const pg_net &n);
+int32_t split_scope(const pg_eval_args &a);
+
+// [6, H1, H2, O] networks (two hidden layers, H1, H2 <= 512, O in 2..4) on the
+// weight-streaming kernel k_wide (pg_wide.hip); launch_wide runs the sigmoid
+// or the ReLU instance (PG_KERNEL_RELU_WIDE) by p.activation, and wide_scope
+// is that of relu ? RELU_WIDE : WIDE.
 bool wide_shape_ok(const pg_net &n, int n_games);
 size_t wide_workspace_bytes(const pg_eval_args *a);
+int32_t wide_scope(const pg_eval_args &a, bool relu);
 int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s);
 
-// [6, H <= 256, 2..4] ReLU networks with bias on k_relu (pg_relu.hip): the
-// shapes it holds, and its launch (certified precision; no workspace beyond the base)
+// [6, H <= 256, 2..4] ReLU networks with bias on k_relu (pg_relu.hip; certified
+// precision, no workspace beyond the base)
 bool relu_shape_ok(const pg_net &n);
+int32_t relu_scope(const pg_eval_args &a);
 // advance (PG_KERNEL_ADVANCE): the k_*_adv instances, unless the launch is traced;
 // solo (PG_KERNEL_SOLO): the k_*_solo instances, traced or not
 int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
@@ -163,12 +218,11 @@ int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hip
 // [6, 2..64, 2..64, 2..4] ReLU networks with bias on k_relu2 (pg_relu2.hip; the
 // host side it shares with k_sig2 is pg_hidden2.hpp's): the same for two hidden layers
 bool relu2_shape_ok(const pg_net &n);
+int32_t relu2_scope(const pg_eval_args &a);
 int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
-// [6, 2..64, 2..64, 2..4] sigmoid networks with bias on k_sig2 (pg_sig2.hip,
-// pg_hidden2.hpp): the shapes it holds (the bias is checked apart: its refusal
-// has its own message), and its launch (certified precision; no workspace beyond the base)
-bool sig2_shape_ok(const pg_net &n);
+// [6, 2..64, 2..64, 2..4] sigmoid networks with bias on k_sig2 (pg_sig2.hip, pg_hidden2.hpp)
+int32_t sig2_scope(const pg_eval_args &a);
 int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
 // the launches of the k_*_solo / k_*_adv_solo instances (PG_KERNEL_SOLO): each

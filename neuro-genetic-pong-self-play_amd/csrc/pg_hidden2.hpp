@@ -420,7 +420,7 @@ struct Sig2Policy {
 
 // ------------------------------------------------------------ host side ----
 // A family F (Relu2Family in pg_relu2.hip, Sig2Family in pg_sig2.hip) supplies
-// kActivation, its refusals' messages and the launches of its two kernels.
+// kActivation, its refusals' messages and the launches of its kernels.
 
 // the instances: LN = hidden2_lanes(H1, H2) lanes per network, hidden2_units(LN) units of each layer per lane
 #define PG_HIDDEN2_DISPATCH(KERNEL, LN, O, f64, grid, s, p)                                                    \
@@ -438,15 +438,29 @@ inline bool hidden2_shape_ok(int n_nodes, const int32_t *nodes) {
 
 inline long hidden2_genes(int H1, int H2, int O) { return (long)H1 * 7 + (long)H2 * (H1 + 1) + (long)O * (H2 + 1); }
 
+static_assert(4 * hidden2_units(4) >= 16 && 16 * hidden2_units(16) >= 32 && 32 * hidden2_units(32) >= kHidden2MaxH,
+              "hidden2_lanes' thresholds: a layout for every H1, H2 in scope");
+
+// The family's scope (pg_eval.hpp), in its words.  Only the sigmoid family has
+// rules of its own for a horizon and a hard-case log: pg_eval_population
+// refuses both for every ReLU network, after its empty-launch return.
+template <class F>
+int32_t hidden2_scope(const pg_eval_args &a) {
+  if (a.net.activation != F::kActivation) return F::bad_activation();
+  if (!hidden2_shape_ok(a.net.n_nodes, a.net.nodes)) return F::bad_shape();
+  if (!a.net.bias) return F::no_bias();
+  if (a.precision == PG_PREC_F64) return F::no_f64();
+  if constexpr (F::kActivation == PG_ACT_SIGMOID) {
+    if (a.horizon > 0) return F::no_horizon();
+    if (a.hard_log) return F::no_hard_log();
+  }
+  return PG_OK;
+}
+
+// p: a network in hidden2_scope, row strides of at least its gene count (pg_eval_population)
 template <class F>
 int32_t hidden2_launch(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
-  const int H1 = p.nodes[1], H2 = p.nodes[2], O = p.nodes[3];
-  if (!hidden2_shape_ok(p.n_nodes, p.nodes)) return F::bad_shape();
-  if (!p.bias) return F::no_bias();
-  const int LN = hidden2_lanes(H1, H2);
-  if (LN * hidden2_units(LN) < H1 || LN * hidden2_units(LN) < H2) return F::no_layout(H1, H2);
-  const long G = hidden2_genes(H1, H2, O);
-  if (p.gstride < G || (p.n_opponents > 0 && p.ostride < G)) return F::short_stride();
+  const int LN = hidden2_lanes(p.nodes[1], p.nodes[2]), O = p.nodes[3];
   const int grid = cert_game_grid(p, LN);
   if (grid <= 0) return PG_OK;
   // a traced launch records every frame: it runs with the advance off

@@ -105,17 +105,23 @@ bool relu_shape_ok(const pg_net &n) {
          n.nodes[2] <= 4 && n.bias != 0;
 }
 
+static_assert(relu_lanes(kReluMaxH) * kReluUnits >= kReluMaxH, "a layout for every H in scope");
+
+int32_t relu_scope(const pg_eval_args &a) {
+  if (a.net.activation != PG_ACT_RELU)
+    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu kernel evaluates PG_ACT_RELU networks only");
+  if (!relu_shape_ok(a.net))
+    return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
+  if (a.precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "relu kernel is the certified-precision path");
+  return PG_OK;
+}
+
 static long relu_genes(int H, int O) { return (long)H * 7 + (long)O * (H + 1); }
 
+// p: a network in relu_scope, row strides of at least its gene count (pg_eval_population)
 int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
   const int H = p.nodes[1], O = p.nodes[2];
-  if (p.n_nodes != 3 || p.nodes[0] != 6 || H < 1 || H > kReluMaxH || O < 2 || O > 4 || !p.bias)
-    return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
   const int LN = relu_lanes(H);
-  if (LN * kReluUnits < H) return fail(PG_ERR_UNSUPPORTED, "relu kernel: no layout for H=%d", H);
-  const long G = relu_genes(H, O);
-  if (p.gstride < G || (p.n_opponents > 0 && p.ostride < G))
-    return fail(PG_ERR_INVALID, "relu kernel: a row stride is below the gene count");
   const int grid = cert_game_grid(p, LN);
   if (grid <= 0) return PG_OK;
   // a traced launch records every frame: it runs with the advance off

@@ -73,16 +73,14 @@ bool relu2_shape_ok(const pg_net &n) { return hidden2_shape_ok(n.n_nodes, n.node
 
 struct Relu2Family {
   static constexpr int kActivation = PG_ACT_RELU;
+  static int32_t bad_activation() {
+    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu2 kernel evaluates PG_ACT_RELU networks only");
+  }
   static int32_t bad_shape() {
     return fail(PG_ERR_UNSUPPORTED, "relu2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4] with bias");
   }
   static int32_t no_bias() { return bad_shape(); }
-  static int32_t no_layout(int H1, int H2) {
-    return fail(PG_ERR_UNSUPPORTED, "relu2 kernel: no layout for H1=%d H2=%d", H1, H2);
-  }
-  static int32_t short_stride() {
-    return fail(PG_ERR_INVALID, "relu2 kernel: a row stride is below the gene count");
-  }
+  static int32_t no_f64() { return fail(PG_ERR_UNSUPPORTED, "relu2 kernel is the certified-precision path"); }
   static int32_t decide_bad_activation(int activation) {
     return fail(PG_ERR_UNSUPPORTED, "pg_relu2_decide: activation=%d, the relu2 kernel decides PG_ACT_RELU networks only",
                 activation);
@@ -100,6 +98,8 @@ struct Relu2Family {
     PG_HIDDEN2_DISPATCH(k_relu2_decide, LN, O, f64, grid, s, p);
   }
 };
+
+int32_t relu2_scope(const pg_eval_args &a) { return hidden2_scope<Relu2Family>(a); }
 
 int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
   return hidden2_launch<Relu2Family>(p, dtype, advance, solo, s);

@@ -69,19 +69,21 @@ __global__ __launch_bounds__(256) void k_sig2_decide(CertDecideParams p) {
     cert_decide_pass<Sig2Policy<LN, U1, U2, O, WT>>(p, base);
 }
 
-bool sig2_shape_ok(const pg_net &n) { return hidden2_shape_ok(n.n_nodes, n.nodes); }
-
 struct Sig2Family {
   static constexpr int kActivation = PG_ACT_SIGMOID;
+  static int32_t bad_activation() {
+    return fail(PG_ERR_UNSUPPORTED, "activation relu: the sig2 kernel evaluates sigmoid networks only (use RELU2)");
+  }
   static int32_t bad_shape() {
     return fail(PG_ERR_UNSUPPORTED, "sig2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4]");
   }
   static int32_t no_bias() { return fail(PG_ERR_UNSUPPORTED, "sig2 kernel needs a network with bias"); }
-  static int32_t no_layout(int H1, int H2) {
-    return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no layout for H1=%d H2=%d", H1, H2);
+  static int32_t no_f64() { return fail(PG_ERR_UNSUPPORTED, "sig2 kernel is the certified-precision path"); }
+  static int32_t no_horizon() {
+    return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no fixed-horizon mode (horizon must be 0)");
   }
-  static int32_t short_stride() {
-    return fail(PG_ERR_INVALID, "sig2 kernel: a row stride is below the gene count");
+  static int32_t no_hard_log() {
+    return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no hard-case log (hard_log must be NULL)");
   }
   static int32_t decide_bad_activation(int activation) {
     return fail(PG_ERR_UNSUPPORTED, "pg_sig2_decide: activation=%d, the sig2 kernel decides sigmoid networks only",
@@ -102,6 +104,8 @@ struct Sig2Family {
     PG_HIDDEN2_DISPATCH(k_sig2_decide, LN, O, f64, grid, s, p);
   }
 };
+
+int32_t sig2_scope(const pg_eval_args &a) { return hidden2_scope<Sig2Family>(a); }
 
 int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
   return hidden2_launch<Sig2Family>(p, dtype, advance, solo, s);

@@ -882,6 +882,22 @@ bool wide_shape_ok(const pg_net &n, int n_games) {
          n_games >= 1 && n_games <= 64;
 }
 
+// k_wide is exact f64 under either precision: activation and shape only
+int32_t wide_scope(const pg_eval_args &a, bool relu) {
+  if (relu) {
+    if (a.net.activation != PG_ACT_RELU)
+      return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu_wide kernel evaluates PG_ACT_RELU networks only (use WIDE)");
+    if (!wide_shape_ok(a.net, a.n_games))
+      return fail(PG_ERR_UNSUPPORTED, "relu_wide kernel needs NETWORK_SHAPE [6, 2..512, 2..512, 2..4]");
+    return PG_OK;
+  }
+  if (a.net.activation != PG_ACT_SIGMOID)
+    return fail(PG_ERR_UNSUPPORTED, "activation relu: the wide kernel evaluates sigmoid networks only (use RELU, RELU2, RELU_WIDE or GENERAL)");
+  if (!wide_shape_ok(a.net, a.n_games))
+    return fail(PG_ERR_UNSUPPORTED, "wide kernel needs NETWORK_SHAPE [6, H1<=512, H2<=512, 1..4] and n_games <= 8");
+  return PG_OK;
+}
+
 // games per work item (k_wide's NG): with f32 genes 6, so GAMES_TO_PLAY = 6
 // plays a genome's games in one lockstep pass; more games are split into
 // balanced chunks (k_wide<8> spilled 112 VGPRs: round-4 review).  With f64

@@ -2,6 +2,7 @@
 .so travels with the repository snapshot to the GPU box)."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -9,17 +10,19 @@ import sys
 from ._lib import LIB_PATH, PKG_DIR, REPO_DIR
 
 CSRC = os.path.join(PKG_DIR, "csrc")
-HEADERS = [os.path.join(CSRC, h) for h in ("pg_device.hpp", "pg_f64math.h", "pg_eval.hpp", "pg_cascade.hpp",
-                                           "pg_service.hpp", "pg_certgame.hpp", "pg_relu.hpp", "pg_relu_bound.h",
-                                           "pg_hidden2.hpp", "pg_relu2_bound.h", "pg_sig2_bound.h")] + [os.path.join(REPO_DIR, "include", "pong_ga.h")]
-# one translation unit per kernel family, compiled in parallel and linked into one .so;
+# every header there is: one that a hand-kept list missed would leave stale objects behind
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [
+    os.path.join(REPO_DIR, "include", "pong_ga.h")]
+# one translation unit per concern (csrc/pg_eval.hpp maps them), compiled in parallel and linked into one .so;
+# a .cpp unit is plain host C++;
 # pg_service_more.hip is compiled once per (lanes per game, genome type): its ~100
 # k_service instantiations took 10 minutes as one unit
 # the certified families' sources are compiled twice: with -DPG_SOLO_UNIT a unit
 # holds only the family's k_*_solo instances (PG_KERNEL_SOLO), so the first
 # object's kernels stay what they were and the two compile side by side
 # (object name, source, extra flags)
-UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_wide", "pg_wide.hip", []), ("pg_pixels", "pg_pixels.hip", []),
+UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_general", "pg_general.hip", []), ("pg_ga", "pg_ga.hip", []),
+         ("pg_hof_scan", "pg_hof_scan.cpp", []), ("pg_wide", "pg_wide.hip", []), ("pg_pixels", "pg_pixels.hip", []),
          ("pg_hof", "pg_hof.hip", []), ("pg_gen", "pg_gen.hip", []), ("pg_decide", "pg_decide.hip", []),
          ("pg_relu", "pg_relu.hip", []), ("pg_relu2", "pg_relu2.hip", []),
          ("pg_sig2", "pg_sig2.hip", []), ("pg_relu_solo", "pg_relu.hip", ["-DPG_SOLO_UNIT"]),
@@ -37,7 +40,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (pg_service_more.hip keeps the default scheduler: iterative-ilp crashes the
 # register allocator on some small k_service layouts in this compiler, so
 # pong_ga.hip instantiates only the bench layout)
-SOURCE_FLAGS = {"pong_ga.hip": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]}
+# (pg_general.hip and pg_ga.hip hold kernels that were pong_ga.hip's: under the
+# flag they compile to what they were there; without it k_vary<float> differs
+# in 5 739 of its 5 963 lines)
+_ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
+SOURCE_FLAGS = {"pong_ga.hip": _ILP, "pg_general.hip": _ILP, "pg_ga.hip": _ILP}
 ARCH = os.environ.get("PG_OFFLOAD_ARCH", "gfx950")
 
 
@@ -45,16 +52,20 @@ def _obj(name: str) -> str:
     return os.path.join(CSRC, name + ".o")
 
 
-def _flags() -> list:
-    return [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off"] + [
+def _flags(src: str = "") -> list:
+    """The compile flags of source src (tools/build_variant.py builds with them too).
+    A .cpp unit is host C++: no offload arch and no per-source flag."""
+    host = src.endswith(".cpp")
+    return (["-x", "c++"] if host else [f"--offload-arch={ARCH}"]) + ["-O3", "-std=c++17", "-ffp-contract=off"] + [
         # no SLP packing of independent f32 adds into v_pk_add_f32: it breaks the
         # DPP-fused reductions into mov_dpp + pk_add pairs (measured -5 %)
         "-fno-slp-vectorize", "-fPIC",
-        "-Wall", "-Wno-unused-function", "-I", os.path.join(REPO_DIR, "include")]
+        "-Wall", "-Wno-unused-function", "-I", os.path.join(REPO_DIR, "include")] + (
+        [] if host else SOURCE_FLAGS.get(os.path.basename(src), []))
 
 
 def _unit_cmd(src: str, extra: list, out: str) -> list:
-    return [HIPCC] + _flags() + SOURCE_FLAGS.get(os.path.basename(src), []) + extra + ["-c", "-o", out, src]
+    return [HIPCC] + _flags(src) + extra + ["-c", "-o", out, src]
 
 
 def _link_cmd(objs: list, out: str) -> list:

@@ -1,6 +1,6 @@
 """The device GA's counter-based draws restated in numpy (test infrastructure):
 splitmix64 and the keys of k_select / k_select_ranked / k_vary
-(csrc/pong_ga.hip u01, rng_key, rng_u01), so a test can recompute, from the
+(csrc/pg_ga.hip u01, rng_key, rng_u01), so a test can recompute, from the
 same draws, what DEAP's operators (ga.py:89-94: cxBlend, mutGaussian,
 selTournament) give and compare the device's offspring bit for bit."""
 import numpy as np
@@ -25,7 +25,7 @@ def _gen_key(seed, gen):
 
 
 def u01(seed, gen, stream, a, b):
-    """u01(seed, generation, stream, a, b) of pong_ga.hip (k_select / k_select_ranked)."""
+    """u01(seed, generation, stream, a, b) of pg_ga.hip (k_select / k_select_ranked)."""
     with np.errstate(over="ignore"):
         k = splitmix64(np.uint64(_gen_key(seed, gen)) ^ ((np.uint64(stream) * np.uint64(C_STREAM)) + np.asarray(a, np.uint64)))
     k = splitmix64(k ^ np.asarray(b, np.uint64))
@@ -33,7 +33,7 @@ def u01(seed, gen, stream, a, b):
 
 
 def rng_key(seed, gen, stream, a):
-    """rng_key(seed, generation, stream, a) of pong_ga.hip (k_vary)."""
+    """rng_key(seed, generation, stream, a) of pg_ga.hip (k_vary)."""
     with np.errstate(over="ignore"):
         return splitmix64(np.uint64(_gen_key(seed, gen)) ^ ((np.uint64(stream) * np.uint64(C_STREAM)) + np.asarray(a, np.uint64)))
 

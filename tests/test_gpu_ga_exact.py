@@ -1,5 +1,5 @@
 """The device GA operators pinned by exact arithmetic (A11 / (f)1): from the
-same counter-based draws (tests/_ga_draws.py restates pong_ga.hip's keys in
+same counter-based draws (tests/_ga_draws.py restates pg_ga.hip's keys in
 numpy), DEAP's own operator code -- pong_amd.deap_compat.tools.cxBlend and
 mutGaussian, restated from DEAP (ga.py:89-92), driven by a stub ``random``
 that hands them those draws -- gives every offspring gene of pg_ga_vary bit

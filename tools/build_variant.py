@@ -21,13 +21,11 @@ def main(argv):
     out_dir = os.path.join(REPO, "ab")
     obj_dir = os.path.join(out_dir, name + ".obj")
     os.makedirs(obj_dir, exist_ok=True)
-    flags = [f"--offload-arch={B.ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC",
-             "-Wall", "-Wno-unused-function", "-I", os.path.join(B.REPO_DIR, "include")] + extra
     procs, objs = [], []
     for uname, src, uflags in B.UNITS:
         src = os.path.join(B.CSRC, src)
         obj = os.path.join(obj_dir, uname + ".o")
-        cmd = [B.HIPCC] + flags + B.SOURCE_FLAGS.get(os.path.basename(src), []) + uflags + ["-c", "-o", obj, src]
+        cmd = [B.HIPCC] + B._flags(src) + extra + uflags + ["-c", "-o", obj, src]
         procs.append((subprocess.Popen(cmd), cmd))
         objs.append(obj)
     for p, cmd in procs:

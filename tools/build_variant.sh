@@ -9,9 +9,10 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 C=$ROOT/neuro-genetic-pong-self-play_amd/csrc
 TU=${PG_TU:-pong_ga.hip}
 mkdir -p $ROOT/ab
-# the main build's machine scheduler for pong_ga.hip (pong_amd/build.py SOURCE_FLAGS); PG_SCHED overrides
-if [ "$TU" = "pong_ga.hip" ]; then SCHED=${PG_SCHED:-iterative-ilp}; else SCHED=${PG_SCHED:-}; fi
-SFLAG=""; [ -n "$SCHED" ] && SFLAG="-mllvm -amdgpu-sched-strategy=$SCHED"
+# the main build's per-source flags for this unit (pong_amd/build.py SOURCE_FLAGS: the machine scheduler);
+# PG_SCHED names another scheduler
+SFLAG=$(cd $ROOT/neuro-genetic-pong-self-play_amd && python3 -c "from pong_amd import build as B; print(' '.join(B.SOURCE_FLAGS.get('$TU', [])))")
+[ -n "$PG_SCHED" ] && SFLAG="-mllvm -amdgpu-sched-strategy=$PG_SCHED"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall \
   -Wno-unused-function -I $ROOT/include $SFLAG "$@" -c -o /tmp/pg_variant_$NAME.o $C/$TU
 OBJS="/tmp/pg_variant_$NAME.o"
