@@ -23,6 +23,8 @@
  *                                numpy_nn.py:120-137, keep_within_game_bounds
  *                                utils.py:71-77, calculate_timeout_and_frames
  *                                main.py:128-135, calculate_reward utils.py:104-109
+ * pg_eval_resolve                (host only) the kernel and the modifier bits a pg_eval_population call with
+ *                                these arguments runs with: PG_KERNEL_AUTO and PG_KERNEL_SOLO resolved
  * pg_forward                     NeuralNetwork.run numpy_nn.py:120-137 (batched)
  * pg_decide                      get_actions' model.run argmax (main.py:143-150) as the
  *                                hot kernel decides it (test / fixture entry point)
@@ -112,7 +114,9 @@ typedef enum pg_precision {
 typedef enum pg_kernel {
   PG_KERNEL_AUTO = 0,      /* SPLIT when the shape and precision allow, else GENERAL (ReLU nets: RELU or RELU2
                               in their scopes; every ReLU net outside them runs on GENERAL under AUTO --
-                              RELU_WIDE is never picked by AUTO, it is chosen explicitly) */
+                              RELU_WIDE is never picked by AUTO, it is chosen explicitly).  AUTO never sets a
+                              modifier bit itself; one OR-ed in takes effect where the kernel it picks has the
+                              instance (PG_KERNEL_SOLO below), and pg_eval_resolve reports what a call runs */
   PG_KERNEL_GENERAL = 1,   /* one wave per game, f64, any NETWORK_SHAPE */
   PG_KERNEL_RESIDENT = 2,  /* retired (round 4): PG_ERR_UNSUPPORTED */
   PG_KERNEL_SPLIT = 3      /* [6, H<=256, 2..4]: half a lane group per paddle's network; f32 forwards with
@@ -176,11 +180,20 @@ enum {
                                the scope, the refusals and their messages are the base kernel's, the workspace is
                                the same (the second game counter lives in its 256-byte header); PG_KERNEL_AUTO
                                with the bit resolves exactly as without it, solo where it picks RELU or RELU2,
-                               no change where it picks SPLIT, WIDE or GENERAL; every other explicit kernel with
+                               no change where it picks WIDE or GENERAL; every other explicit kernel with
                                the bit: PG_ERR_UNSUPPORTED (after the advance bit's refusal when both are set;
                                checked even for an empty launch).  The two bits combine freely.  A traced launch
                                keeps solo on (it steps every frame); with both bits it runs the solo kernel
-                               without the advance */
+                               without the advance.
+                               Where AUTO picks SPLIT the bit plays such games on half a lane group
+                               of k_service's 8-lane layout, again with every output and all 16 counters the base
+                               instance's, on the launches in the solo scope: nodes[1] in 33..64, group_lanes 0
+                               or 8, horizon 0, trace NULL, hard_log NULL.  Every other SPLIT launch under
+                               AUTO | SOLO -- traced, fixed-horizon, logged, another width or lane count -- runs
+                               the base instance, which is not an error (PG_KERNEL_ADVANCE stays ignored there).
+                               An explicit PG_KERNEL_SPLIT | PG_KERNEL_SOLO is still PG_ERR_UNSUPPORTED: the
+                               asymmetry is deliberate for now, the refusal is pinned by recorded messages.
+                               pg_eval_resolve tells whether the bit applies to a call */
 };
 
 /* pg_eval_args.prep: the SPLIT kernel's lane records (one per network of the
@@ -578,6 +591,13 @@ size_t pg_eval_workspace_bytes(const pg_eval_args *args);
 int32_t pg_gene_count(const pg_net *net);
 
 int32_t pg_eval_population(const pg_eval_args *args, void *stream);
+/* The pg_kernel pg_eval_population launches for these arguments (PG_KERNEL_AUTO resolved), OR-ed with
+ * the modifier bits that take effect on that launch; a negative pg_status (message in pg_last_error)
+ * where pg_eval_population refuses the arguments before its buffer checks.  Host only: it reads the
+ * struct's values and follows none of its pointers (trace and hard_log count as set or NULL), so it
+ * may be asked before anything is allocated.  A scope that pg_eval_population checks only at the
+ * launch (an explicit PG_KERNEL_SPLIT, WIDE or RELU outside its shapes) is not anticipated here. */
+int32_t pg_eval_resolve(const pg_eval_args *args);
 int32_t pg_forward(const pg_forward_args *args, void *stream);
 int32_t pg_decide(const pg_decide_args *args, void *stream);
 size_t pg_wide_decide_workspace_bytes(const pg_wide_decide_args *args);

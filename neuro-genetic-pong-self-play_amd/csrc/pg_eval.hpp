@@ -7,6 +7,7 @@
 //                        and the kernels its generated code depends on
 //                        (k_forward_resident, k_physics_* with pg_physics_*)
 //   pg_service_more.hip  every other k_service instance
+//   pg_service_solo.hip  k_service's solo instances (PG_KERNEL_SOLO on the bench layout)
 //   pg_general.hip       the f64 path: k_general, pg_forward with k_forward_general
 //   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
 //   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
@@ -197,6 +198,9 @@ int32_t launch_forward_resident(const FwdParams &p, int dtype, hipStream_t s);
 // [6, H <= 256, 2..4] sigmoid networks on k_service (SPLIT; pong_ga.hip, pg_service_more.hip)
 bool resident_shape_ok(const pg_net &n);
 int32_t split_scope(const pg_eval_args &a);
+// the split launches that PG_KERNEL_SOLO (through PG_KERNEL_AUTO) plays on k_service's solo instances
+// (pg_service_solo.hip); outside it the bit changes nothing on SPLIT
+bool split_solo_scope(const pg_eval_args &a);
 
 // [6, H1, H2, O] networks (two hidden layers, H1, H2 <= 512, O in 2..4) on the
 // weight-streaming kernel k_wide (pg_wide.hip); launch_wide runs the sigmoid

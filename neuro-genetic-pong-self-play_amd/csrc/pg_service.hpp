@@ -5,7 +5,8 @@
 // pong_ga.hip instantiates the [6,<=64,O] bench layout L=8, U=16 under the
 // iterative-ILP scheduler; pg_service_more.hip the other (L, U) layouts under
 // the default one (the iterative scheduler's register allocation crashes the
-// ROCm 7.2 compiler on some of them).
+// ROCm 7.2 compiler on some of them).  pg_service_solo.hip holds the bench
+// layout's kSolo instances (PG_KERNEL_SOLO), a unit of its own again.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -222,16 +223,146 @@ __device__ __forceinline__ void pg_probe_extra(float2v w, float2v w2, float a, f
 }
 #endif
 
+// ------------------------------------------- kSolo's game queues ----
+// Two cursors in the work header walk all game indices, p.work[0] for the
+// kOppNN games and p.work[1] for the others, as cert_take's do -- but a wave
+// claims a span of indices per atomic, reads the span's kinds in one coalesced
+// load and keeps the span's games of the cursor's sort as a 64-bit mask, from
+// which its groups (NN games) and half-groups (the others) are served.  The
+// span is remaining / (4 waves) indices while the launch is young, at most
+// kSoloSpanYoung = 16 (two per group of the wave), and never less than two
+// indices per lane group or half that waits for a game, so the groups of a
+// starting wave are served by one claim; it doubles while a claim finds no game
+// of the cursor's sort, up to 64 (a lane each).  "remaining" is counted from
+// the wave's previous span, not read again (a second round trip): it is as old
+// as the wave's last claim, and 16 indices are what the wave's own groups use
+// up in about one round of games, so the estimate lags by about one round of
+// 12 at 65 536 genomes.  Near the launch's end a wave so claims 2 indices for a
+// free taker, or one or two more while its estimate lags, and holds that many
+// games its lanes are too busy to play.  A launch issues at most total / 2
+// atomics and one per wave on each cursor: fewer than the base kernel's one
+// per game and one per group at its exit.  (One round trip per claim matters more than their
+// number: every wave of the launch claims at its start and again when the NN
+// cursor runs out, and a round trip then waits for all of theirs.)
+constexpr unsigned kSoloSpanYoung = 16;
+struct SoloQueue {        // one per wave, in LDS
+  uint64_t mask[2];       // the claimed span's unplayed games: [0] kOppNN, [1] the others
+  int base[2];            // the span's first index
+  int done[2];            // the cursor has passed the last game
+};
+template <int N>
+__device__ __forceinline__ SoloQueue *solo_queue_lds() {
+  __shared__ SoloQueue q[N];
+  return q;
+}
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+// the next span of cursor Q that holds a game of its sort, by the whole wave, for takers waiting
+// groups or halves; done: there is none
+template <int Q>
+__device__ __forceinline__ void solo_refill(const EvalParams &p, int games_total, int lane64, int takers, uint64_t &mask,
+                                            int &base, int &done) {
+  const unsigned waves = gridDim.x * (blockDim.x >> 6);
+  unsigned span = (unsigned)(games_total - base) / (4u * waves);
+  span = span > kSoloSpanYoung ? kSoloSpanYoung : span;
+  span = span < 2u * (unsigned)takers ? 2u * (unsigned)takers : span;
+  for (;; span *= 2u) {
+    span = span > 64u ? 64u : span;
+    unsigned w0 = 0;
+    if (lane64 == 0) w0 = atomicAdd(p.work + Q, span);
+    w0 = (unsigned)__builtin_amdgcn_readfirstlane((int)w0);
+    if (w0 >= (unsigned)games_total) break;
+    const bool in = (unsigned)lane64 < span && w0 + (unsigned)lane64 < (unsigned)games_total;
+    const int kd = in ? p.kind[w0 + lane64] : 0;
+    mask = __builtin_amdgcn_ballot_w64(in && (kd == kOppNN) == (Q == 0));
+    base = (int)w0;
+    if (mask) return;
+  }
+  done = 1;
+}
+// the left half of a pair game: its right half counts the game and writes its results
+__device__ __forceinline__ bool solo_second(int side, int kind) { return side && kind == kOppNN; }
+// a game's first lane: hl == 0 of a solo game, lig == 0 of a pair game
+__device__ __forceinline__ bool solo_first(int hl, int side, int kind) { return hl == 0 && !solo_second(side, kind); }
+
+// Games for the wave's free lanes (want), by the whole wave: a free group takes
+// a kOppNN game while that cursor lasts (both its halves came free at the same
+// frame: no half of the wave plays alone before); from then on each half takes
+// one of the other games on its own.  True, and the game in w, where one was left.
+template <int L>
+__device__ __forceinline__ bool solo_take(const EvalParams &p, SoloQueue *q, int games_total, int lane64, bool want,
+                                          int &w) {
+  uint64_t m0 = uniform64(q->mask[0]), m1 = uniform64(q->mask[1]);
+  int b0 = __builtin_amdgcn_readfirstlane(q->base[0]), b1 = __builtin_amdgcn_readfirstlane(q->base[1]);
+  int d0 = __builtin_amdgcn_readfirstlane(q->done[0]), d1 = __builtin_amdgcn_readfirstlane(q->done[1]);
+  bool got = false;
+  if (!d0) {
+    uint64_t takers = __builtin_amdgcn_ballot_w64(want && (lane64 & (L - 1)) == 0);
+#pragma unroll 1
+    while (takers) {
+      if (!m0) solo_refill<0>(p, games_total, lane64, __builtin_popcountll(takers), m0, b0, d0);
+      if (d0) break;
+      const int src = (int)__builtin_ctzll(takers);
+      takers &= takers - 1;
+      if ((lane64 & ~(L - 1)) == src) {
+        w = b0 + (int)__builtin_ctzll(m0);
+        got = true;
+      }
+      m0 &= m0 - 1;
+    }
+  }
+  if (d0 && !d1) {
+    uint64_t takers = __builtin_amdgcn_ballot_w64(want && !got && (lane64 & (L / 2 - 1)) == 0);
+#pragma unroll 1
+    while (takers) {
+      if (!m1) solo_refill<1>(p, games_total, lane64, __builtin_popcountll(takers), m1, b1, d1);
+      if (d1) break;
+      const int src = (int)__builtin_ctzll(takers);
+      takers &= takers - 1;
+      if ((lane64 & ~(L / 2 - 1)) == src) {
+        w = b1 + (int)__builtin_ctzll(m1);
+        got = true;
+      }
+      m1 &= m1 - 1;
+    }
+  }
+  if (lane64 == 0) {
+    q->mask[0] = m0;
+    q->mask[1] = m1;
+    q->base[0] = b0;
+    q->base[1] = b1;
+    q->done[0] = d0;
+    q->done[1] = d1;
+  }
+  return got;
+}
+
 // kUntraced: a launch without a trace buffer (the GA's), the trace tests
 // compiled out of the frame instead of tested on p.trace every frame.
 // kHorizon: SURVEY 8(d)'s fixed-horizon measurement mode (pg_eval_args.horizon,
 // untraced): every game slot runs exactly p.horizon frames, episodes auto-reset,
 // nothing is advanced in closed form.
-template <int L, int U, int O, typename WT, bool kUntraced = false, bool kHorizon = false>
+//
+// kSolo (PG_KERNEL_SOLO under AUTO; the kInline, untraced,
+// non-horizon frame only): a game against a scripted opponent or the ROM CPU
+// has no left network, so a half-group plays it alone -- role 0, whichever half
+// it is: the genome's record, which the idle half loads anyway, and unmirrored
+// features -- and only a kOppNN game takes the whole group (pair: kind ==
+// kOppNN, a parked half included).  Every game variable below is uniform over
+// the lanes that play the game, sframe stays the wave's; the Brent search, the
+// memo and the record index are the half's own slot's in a solo game; the
+// game's first lane (hl == 0 of a solo game, lig == 0 of a pair game) writes
+// its results and counts it.  Games come from solo_take's two queues.  No half
+// ever waits for its sibling: no barrier, no spin.  The per-game work is the
+// base instance's, so the outputs and all 16 counters are too.
+template <int L, int U, int O, typename WT, bool kUntraced = false, bool kHorizon = false, bool kSolo = false>
 __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
   constexpr int kSvcThreads = svc_threads<U>();
   constexpr bool kInline = inline_service<L, U, kHorizon>();
   static_assert(!kInline || O <= 4, "InlineReq.z");
+  static_assert(!kSolo || (kInline && kUntraced && !kHorizon), "kSolo: the inline, untraced, non-horizon frame");
   constexpr int kSvcGameWaves = kSvcThreads / 64 - (kInline ? 0 : 1);
   constexpr int HL = L / 2;
   constexpr int kSlots = kSvcGameWaves * (64 / L) * 2;
@@ -260,6 +391,15 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
   if (threadIdx.x == 0) {
     lds_st(&waves_done, 0);
     lds_st(&posted, 0);
+  }
+  [[maybe_unused]] SoloQueue *sq = nullptr;  // this wave's queues (kSolo)
+  if constexpr (kSolo) {
+    sq = solo_queue_lds<kSvcThreads / 64>() + wave;
+    if (lane64 == 0) {
+      sq->mask[0] = sq->mask[1] = 0;
+      sq->base[0] = sq->base[1] = 0;
+      sq->done[0] = sq->done[1] = 0;
+    }
   }
   __syncthreads();
 
@@ -404,7 +544,10 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
 
   const int games_total = active_total(p);
   int w;
-  {
+  if constexpr (kSolo) {
+    w = games_total;
+    solo_take<L>(p, sq, games_total, lane64, true, w);
+  } else {
     int ww = 0;
     if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
     w = group_broadcast<L>(ww, leader);
@@ -510,7 +653,11 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
       tend = sframe + p.timeout_thresh;  // frame 1 does not count (main.py:94-96): it takes the counter to 0
       fresh = false;
       if (hl == 0) slots[sx].n_memo = 0;
-      if (lig == 0) slots[sx].rally_at = -1;  // (sx is the side-0 slot there)
+      if constexpr (kSolo) {
+        if (solo_first(hl, side, kind)) slots[sx].rally_at = -1;  // the game's first lane: its own slot
+      } else {
+        if (lig == 0) slots[sx].rally_at = -1;  // (sx is the side-0 slot there)
+      }
       if (kHorizon && lig == 0) {
         const int gx = threadIdx.x / L;
         hz[gx].sum = 0.0;
@@ -543,7 +690,8 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
         act_l = clamp_move(st.lc2, 0);  // (a 1-player env's CPU paddle: unclipped, the same side of the band)
         fstart -= h;  // frames += h, and the no-score counter with them
         tend -= h;
-        hidden += h;
+        if constexpr (kSolo) hidden += solo_second(side, kind) ? 0 : h;  // (summed by hl == 0 lanes: a pair game once)
+        else hidden += h;
       }
     }
 #endif
@@ -587,7 +735,9 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
       pg_probe_extra<PG_PROBE_EXTRA>(net.w1[0][0], net.w1[1][1], z[0], z[1], probe_v, probe_p, probe_s);
 #endif
       const bool left_nn = kind == kOppNN;
-      if (side && !left_nn) code = 0;  // the left half is idle against a scripted opponent
+      if constexpr (!kSolo) {
+        if (side && !left_nn) code = 0;  // the left half is idle against a scripted opponent
+      }
       if (vis != 1) code = 0;  // the ball hidden ([0,0]) or a parked group
 #ifdef PG_ABLATE_SLOW  // timing-only build: never re-decide in f64
       if (code == -1) code = z[1] > z[0] ? 6 : -6;
@@ -634,8 +784,10 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
           code = hit;
         }
         // the request: the network's own features (x-flipped for the left paddle), its f32 outputs and bound
-        const int kn[6] = {side ? 320 - bx2 : bx2, by2, side ? 320 - lbx2 : lbx2, lby2, side ? lc2 : rc2,
-                           side ? rc2 : lc2};
+        // (kSolo: a half playing alone is the right paddle, whichever half it is)
+        const int role = kSolo ? (left_nn ? side : 0) : side;
+        const int kn[6] = {role ? 320 - bx2 : bx2, by2, role ? 320 - lbx2 : lbx2, lby2, role ? lc2 : rc2,
+                           role ? rc2 : lc2};
         const float my_e = net.e;
         uint64_t need = __builtin_amdgcn_ballot_w64(code == -1 && hl == 0);
         if (need) {
@@ -755,9 +907,16 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
       }
       }
       const int mine = code;
-      const int other = other_half<L>(mine);
-      right = side ? other : mine;
-      left = side ? mine : other;
+      const int other = other_half<L>(mine);  // (kSolo: used in a pair game only; a solo game's left is set below)
+      if constexpr (kSolo) {
+        right = side && left_nn ? other : mine;
+        left = side && left_nn ? mine : other;
+        // (a parked half, its sibling playing on: neither paddle moves; every game's moves are 0 here already)
+        if (vis != 1) right = left = 0;
+      } else {
+        right = side ? other : mine;
+        left = side ? mine : other;
+      }
       // HardcodedAi / ScoreHardcodedAi (dumb_ais.py): behind a wave-uniform
       // test, which a self-play schedule never passes
       if (__builtin_expect(w_scripted, 0) && !left_nn) {
@@ -817,16 +976,22 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
       // only by the scores (round-5 review: `over` kept the pre-point timeout)
       over = st.s1 >= p.win_score || st.s2 >= p.win_score || st.done();
       if constexpr (kHorizon) over = over || sframe - fstart >= p.horizon;
-      if (lig == 0) slots[slot_grp()].rally_at = -1;  // the next rally searches afresh
+      if constexpr (kSolo) {
+        if (solo_first(hl, side, kind)) slots[slot_me()].rally_at = -1;
+      } else {
+        if (lig == 0) slots[slot_grp()].rally_at = -1;  // the next rally searches afresh
+      }
     }
 #ifndef PG_NO_RALLY_SKIP
     const int timeout = sframe - (tend - p.timeout_thresh);
     if (rally_check && timeout <= p.timeout_thresh) {
-      const int rs = slot_grp();  // the group's side-0 slot
+      // the group's side-0 slot; kSolo: a solo game's half's own, written by the game's first lane
+      const int rs = kSolo && kind != kOppNN ? slot_me() : slot_grp();
+      const bool rw = kSolo ? solo_first(hl, side, kind) : lig == 0;
       const uint64_t key = st.key(move_code(act_r), move_code(act_l));
       const int at = slots[rs].rally_at;
       if (at > timeout || at < 0) {
-        if (lig == 0) {
+        if (rw) {
           slots[rs].rally_key = key;
           slots[rs].rally_at = timeout;
           slots[rs].rally_span = kRallySpan0;
@@ -834,10 +999,11 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
       } else if (slots[rs].rally_key == key) {
         const int rest = p.timeout_thresh + 1 - timeout;
         fstart -= rest;  // frames += rest; the counter at TIMEOUT_THRESH + 1
-        skipped += rest;
+        if constexpr (kSolo) skipped += solo_second(side, kind) ? 0 : rest;
+        else skipped += rest;
         tend = sframe - 1;
       } else if (timeout - at >= slots[rs].rally_span) {
-        if (lig == 0) {
+        if (rw) {
           slots[rs].rally_key = key;
           slots[rs].rally_at = timeout;
           slots[rs].rally_span = 2 * slots[rs].rally_span;
@@ -881,6 +1047,8 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
           p.total_frames[w] = (double)hz[gx].eps;
           p.status_game[w] = hz[gx].zd;
         }
+      } else if constexpr (kSolo) {
+        if (solo_first(hl, side, kind)) finish_game(p, w, st, sframe - fstart, total);
       } else {
         if (lig == 0) finish_game(p, w, st, sframe - fstart, total);
       }
@@ -897,23 +1065,45 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
         }
       }
 #endif
-      c_steps += sframe - fstart;
-      const int vis_frames = kVisByFrames ? sframe - c_vis - (st.s1 + st.s2) : c_vis;
-      c_fwd += (kind == kOppNN ? 2u : 1u) * (uint32_t)vis_frames;
-      c_games += 1;
-      int ww = 0;
-      if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
-      w = group_broadcast<L>(ww, leader);
-      if constexpr (kInline) {
-        if (w >= games_total) {
-          live = false;
-          park();
+      if constexpr (kSolo) {  // (counted by the game's first lane alone: the hl == 0 lanes report)
+        const bool second = solo_second(side, kind);
+        const int vis_frames = kVisByFrames ? sframe - c_vis - (st.s1 + st.s2) : c_vis;
+        c_steps += second ? 0 : sframe - fstart;
+        c_fwd += second ? 0u : (kind == kOppNN ? 2u : 1u) * (uint32_t)vis_frames;
+        c_games += second ? 0 : 1;
+      } else {
+        c_steps += sframe - fstart;
+        const int vis_frames = kVisByFrames ? sframe - c_vis - (st.s1 + st.s2) : c_vis;
+        c_fwd += (kind == kOppNN ? 2u : 1u) * (uint32_t)vis_frames;
+        c_games += 1;
+        int ww = 0;
+        if (lig == 0) ww = (int)atomicAdd(p.work, 1u);
+        w = group_broadcast<L>(ww, leader);
+        if constexpr (kInline) {
+          if (w >= games_total) {
+            live = false;
+            park();
+          } else {
+            fresh = true;
+          }
         } else {
+          if (w >= games_total) break;
           fresh = true;
         }
-      } else {
-        if (w >= games_total) break;
-        fresh = true;
+      }
+    }
+    if constexpr (kSolo) {
+      // the next games of the halves that ended one, by the whole wave (solo_take); none left: the half parks
+      if (__builtin_amdgcn_ballot_w64(over) != 0) {
+        const bool got = solo_take<L>(p, sq, games_total, lane64, over, w);
+        if (over) {
+          if (got) {
+            fresh = true;
+          } else {
+            live = false;
+            park();
+          }
+        }
       }
     }
     if constexpr (kInline) {
@@ -923,8 +1113,8 @@ __global__ __launch_bounds__(svc_threads<U>()) void k_service(EvalParams p) {
     top = __builtin_amdgcn_readfirstlane(__builtin_amdgcn_ballot_w64(fresh || (kJumps && !st.vis && st.timer >= 2)) != 0);
     }
   }
-  if (p.counters && c_games) {
-    if (lig == 0) {
+  if (p.counters && (kSolo || c_games)) {  // (kSolo: a left half reports its pair games' decisions, and counted no game)
+    if (kSolo ? hl == 0 && c_games : lig == 0) {
       // env steps stepped one at a time: the episodes' frames minus those a
       // periodic rally skipped [8] and the serve delays advanced at once [12]
       atomicAdd((unsigned long long *)&p.counters[0], (unsigned long long)(c_steps - skipped - hidden));
@@ -980,10 +1170,16 @@ inline size_t service_records_bytes(int n_genomes, int n_opponents, int L, int U
   return ((size_t)n_genomes + (size_t)(n_opponents > 0 ? n_opponents : 0)) * (size_t)(L / 2) * F * sizeof(float);
 }
 
+// the kSolo instances' launch (pg_service_solo.hip: k_service<8, 16, O, WT, true, false, true>, O in 2..4);
+// service_solo_routed: the (O, genome type) that have one, the others run the base instance
+void service_solo_game(int O, bool f64, int grid, size_t lds, hipStream_t s, const EvalParams &p);
+inline bool service_solo_routed(int O, bool f64) { return O >= 2 && O <= 4; }
+
 // kSplitTrace: instantiate the untraced frame too and launch it when p.trace
 // is null (the bench layout, pong_ga.hip; the other layouts test p.trace)
+// solo: the kSolo instance instead (pong_ga.hip's split_solo_scope: L = 8, U = 16, untraced, no horizon)
 template <int L, int U, int O, typename WT, bool kSplitTrace = false>
-inline int32_t launch_service(const EvalParams &p, hipStream_t s) {
+inline int32_t launch_service(const EvalParams &p, hipStream_t s, bool solo = false) {
   constexpr int kSvcThreads = svc_threads<U>();
   // game groups per block, and the f64 scratch: the service wave's, or each wave's
   // (the horizon instance keeps the service wave: inline_service<L, U, true>)
@@ -1007,7 +1203,9 @@ inline int32_t launch_service(const EvalParams &p, hipStream_t s) {
     PG_HIP(hipGetLastError());
     return PG_OK;
   }
-  if (kSplitTrace && p.horizon > 0)  // the fixed-horizon mode: the bench layout's untraced instance
+  if (solo)  // (set for split_solo_scope's launches alone, pong_ga.hip: this layout, untraced, no horizon)
+    service_solo_game(O, sizeof(WT) == 8, grid, lds, s, p);
+  else if (kSplitTrace && p.horizon > 0)  // the fixed-horizon mode: the bench layout's untraced instance
     hipLaunchKernelGGL((k_service<L, U, O, WT, true, true>), dim3(grid), dim3(kSvcThreads), lds, s, p);
   else if (kSplitTrace && !p.trace)
     hipLaunchKernelGGL((k_service<L, U, O, WT, true>), dim3(grid), dim3(kSvcThreads), lds, s, p);
@@ -1018,7 +1216,7 @@ inline int32_t launch_service(const EvalParams &p, hipStream_t s) {
 }
 
 // layouts L != 8 or U != 16 (pg_service_more.hip); PG_ERR_UNSUPPORTED when none fits
-int32_t launch_service_more(const EvalParams &p, int L, int O, bool f64, hipStream_t s);
+int32_t launch_service_more(const EvalParams &p, int L, int O, bool f64, hipStream_t s, bool solo = false);
 
 // the units per lane the split dispatch instantiates for (L, H): launch_service_any
 // (pong_ga.hip: L = 8 with H in (32, 64] -> 16) and launch_more (pg_service_more.hip:

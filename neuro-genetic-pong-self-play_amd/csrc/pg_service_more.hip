@@ -22,7 +22,7 @@ namespace pg {
 #define PG_MORE_CAT(a, b, c) PG_MORE_CAT2(a, b, c)
 #define PG_MORE_FN PG_MORE_CAT(launch_more_L, PG_MORE_L, PG_MORE_F64)
 
-int32_t PG_MORE_FN(const EvalParams &p, int O, hipStream_t s) {
+int32_t PG_MORE_FN(const EvalParams &p, int O, hipStream_t s, bool solo) {
   using WT = std::conditional<PG_MORE_F64 != 0, double, float>::type;
   constexpr int L = PG_MORE_L;
   const int H = p.nodes[1];
@@ -34,8 +34,8 @@ int32_t PG_MORE_FN(const EvalParams &p, int O, hipStream_t s) {
   }
   if constexpr (L == 8) {
     if (H > 32 && H <= 64) {  // the bench layout's O = 2 / 4 instances (O = 3: pong_ga.hip)
-      if (O == 2) return launch_service<8, 16, 2, WT>(p, s);
-      if (O == 4) return launch_service<8, 16, 4, WT>(p, s);
+      if (O == 2) return launch_service<8, 16, 2, WT>(p, s, solo);
+      if (O == 4) return launch_service<8, 16, 4, WT>(p, s, solo);
       return fail(PG_ERR_UNSUPPORTED, "no service kernel for L=%d H=%d O=%d", L, H, O);
     }
   }
@@ -46,17 +46,17 @@ int32_t PG_MORE_FN(const EvalParams &p, int O, hipStream_t s) {
 
 #ifdef PG_MORE_DISPATCH
 #define PG_MORE_DECL(LL)                                                  \
-  int32_t launch_more_L##LL##_0(const EvalParams &p, int O, hipStream_t s); \
-  int32_t launch_more_L##LL##_1(const EvalParams &p, int O, hipStream_t s);
+  int32_t launch_more_L##LL##_0(const EvalParams &p, int O, hipStream_t s, bool solo); \
+  int32_t launch_more_L##LL##_1(const EvalParams &p, int O, hipStream_t s, bool solo);
 PG_MORE_DECL(8) PG_MORE_DECL(16) PG_MORE_DECL(32) PG_MORE_DECL(64)
 #undef PG_MORE_DECL
 
-int32_t launch_service_more(const EvalParams &p, int L, int O, bool f64, hipStream_t s) {
+int32_t launch_service_more(const EvalParams &p, int L, int O, bool f64, hipStream_t s, bool solo) {
   switch (L) {
-    case 8: return f64 ? launch_more_L8_1(p, O, s) : launch_more_L8_0(p, O, s);
-    case 16: return f64 ? launch_more_L16_1(p, O, s) : launch_more_L16_0(p, O, s);
-    case 32: return f64 ? launch_more_L32_1(p, O, s) : launch_more_L32_0(p, O, s);
-    case 64: return f64 ? launch_more_L64_1(p, O, s) : launch_more_L64_0(p, O, s);
+    case 8: return f64 ? launch_more_L8_1(p, O, s, solo) : launch_more_L8_0(p, O, s, solo);
+    case 16: return f64 ? launch_more_L16_1(p, O, s, solo) : launch_more_L16_0(p, O, s, solo);
+    case 32: return f64 ? launch_more_L32_1(p, O, s, solo) : launch_more_L32_0(p, O, s, solo);
+    case 64: return f64 ? launch_more_L64_1(p, O, s, solo) : launch_more_L64_0(p, O, s, solo);
   }
   return fail(PG_ERR_UNSUPPORTED, "no service kernel for L=%d H=%d O=%d", L, p.nodes[1], O);
 }

@@ -226,7 +226,7 @@ static int choose_split_lanes(int H) {
 }
 
 template <typename WT>
-static int32_t launch_service_any(const EvalParams &p, int L, int O, hipStream_t s) {
+static int32_t launch_service_any(const EvalParams &p, int L, int O, bool solo, hipStream_t s) {
   const int H = p.nodes[1];
   // the bench layout here (H in (32, 64] with L = 8: U = 16 is the smallest
   // that holds it); every other (L, U) in pg_service_more.hip
@@ -237,11 +237,11 @@ static int32_t launch_service_any(const EvalParams &p, int L, int O, hipStream_t
 #endif
   // (only O = 3 here: the iterative scheduler's register allocator crashes
   // ROCm 7.2's compiler on the O = 2 / 4 instances, built in pg_service_more.hip)
-  if (here && O == 3) return launch_service<8, 16, 3, WT, true>(p, s);
+  if (here && O == 3) return launch_service<8, 16, 3, WT, true>(p, s, solo);
 #ifdef PG_DEV_MIN  // variant builds for experiments (tools/build_variant.sh): the bench layout only
   return fail(PG_ERR_UNSUPPORTED, "no service kernel for L=%d H=%d O=%d", L, H, O);
 #else
-  return launch_service_more(p, L, O, sizeof(WT) == 8, s);
+  return launch_service_more(p, L, O, sizeof(WT) == 8, s, solo);
 #endif
 }
 
@@ -255,6 +255,16 @@ int32_t split_scope(const pg_eval_args &a) {
   if (!resident_shape_ok(a.net)) return fail(PG_ERR_UNSUPPORTED, "split kernel needs NETWORK_SHAPE [6, H<=256, 2..4]");
   if (a.precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "split kernel is the certified-precision path");
   return PG_OK;
+}
+
+// PG_KERNEL_SOLO on a launch in split_scope (through PG_KERNEL_AUTO): the launches k_service's solo
+// instances play (pg_service_solo.hip) -- the layout whose game waves decide their own certificate
+// failures (L = 8, U = 16), whole untraced episodes without a hard-case log, and an (O, genome type)
+// that has an instance.  Every other split launch runs the base instance, the bit changing nothing.
+bool split_solo_scope(const pg_eval_args &a) {
+  const int H = a.net.nodes[1];
+  return H >= 33 && H <= 64 && (a.group_lanes == 0 || a.group_lanes == 8) && a.horizon == 0 && !a.trace && !a.hard_log &&
+         service_solo_routed(a.net.nodes[2], a.net.dtype == PG_F64);
 }
 
 // Resident kernel table: (L, U) chosen from the hidden width H.
@@ -337,7 +347,8 @@ static size_t eval_base_workspace(const pg_eval_args *a) {
 }
 
 // the kernel pg_eval_population runs for a (PG_KERNEL_AUTO resolved)
-// (the low byte of pg_eval_args.kernel: PG_KERNEL_ADVANCE and PG_KERNEL_SOLO change no choice and no workspace)
+// (the low byte of pg_eval_args.kernel: PG_KERNEL_ADVANCE and PG_KERNEL_SOLO change no choice and no
+// workspace; which instance of the kernel they select, if any: modifiers_in_effect)
 static int resolve_kernel(const pg_eval_args *a) {
   const int named = a->kernel & 0xff;
   if (named != PG_KERNEL_AUTO) return named;
@@ -358,6 +369,17 @@ static size_t split_records_bytes(const pg_eval_args *a) {
   const int U = (L == 8 && H <= 64) ? 16 : service_units(L, H);  // >= what any build instantiates
   if (U <= 0) return 0;
   return align256(service_records_bytes(a->n_genomes, a->opponents ? a->n_opponents : 0, L, U, a->net.nodes[2]));
+}
+
+// the modifier bits that take effect on kernel (resolve_kernel's) for a launch in its scope:
+// the closed-form advance on the certified f32 families' untraced launches, solo games on theirs and
+// on SPLIT's in split_solo_scope (the bit reaches SPLIT through PG_KERNEL_AUTO only: check_modifier_bits)
+static int modifiers_in_effect(int kernel, const pg_eval_args &a, bool advance, bool solo) {
+  const bool cert = kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2;
+  int bits = 0;
+  if (advance && cert && !a.trace) bits |= PG_KERNEL_ADVANCE;
+  if (solo && (cert || (kernel == PG_KERNEL_SPLIT && split_solo_scope(a)))) bits |= PG_KERNEL_SOLO;
+  return bits;
 }
 
 // ABI 10: the caller's struct must be this header's (pg_eval_args.struct_size)
@@ -407,6 +429,7 @@ static int32_t check_eval_ranges(const pg_eval_args *a) {
 }
 
 // PG_KERNEL_ADVANCE and PG_KERNEL_SOLO go with the certified families' kernels, named or through AUTO
+// (SPLIT takes the solo bit through AUTO only: the refusal of an explicit SPLIT | SOLO is kept for now)
 static bool takes_modifier_bits(int kernel) {
   return kernel == PG_KERNEL_AUTO || kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2;
 }
@@ -513,6 +536,7 @@ static EvalParams eval_params(const pg_eval_args *a) {
 }
 
 // the games on kernel (resolve_kernel's); RELU_WIDE, RELU2 and SIG2 were found in scope on entry
+// (advance, solo: modifiers_in_effect's)
 static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bool advance, bool solo, hipStream_t s) {
   void *const after_base = (char *)a->workspace + eval_base_workspace(a);
   const int dtype = a->net.dtype;
@@ -528,8 +552,8 @@ static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bo
       if (rc != PG_OK) return rc;
       const int L = a->group_lanes > 0 ? a->group_lanes : choose_split_lanes(a->net.nodes[1]);
       p.recs = (float *)after_base;
-      return dtype == PG_F64 ? launch_service_any<double>(p, L, a->net.nodes[2], s)
-                             : launch_service_any<float>(p, L, a->net.nodes[2], s);
+      return dtype == PG_F64 ? launch_service_any<double>(p, L, a->net.nodes[2], solo, s)
+                             : launch_service_any<float>(p, L, a->net.nodes[2], solo, s);
     }
     case PG_KERNEL_RESIDENT:
     case PG_KERNEL_STAGED:
@@ -550,22 +574,38 @@ static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bo
   }
 }
 
-int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
+// pg_eval_population's checks ahead of its n_genomes == 0 return, and pg_eval_resolve's: the ranges,
+// the modifier bits, the scopes asked on entry.  pg_eval_args.kernel is a pg_kernel in the low byte
+// with modifier bits above it: named is the caller's struct with the pg_kernel alone, so every scope
+// check and message after this is the base kernel's
+static int32_t check_eval_entry(const pg_eval_args *a, pg_eval_args &named, bool &advance, bool &solo) {
   if (!a) return fail(PG_ERR_INVALID, "args is NULL");
   int32_t rc = check_eval_ranges(a);
   if (rc != PG_OK) return rc;
-  // pg_eval_args.kernel: a pg_kernel in the low byte, modifier bits above it.  From here on a
-  // is the caller's struct with the pg_kernel alone, so every scope check and message below
-  // is the base kernel's
-  const bool advance = (a->kernel & PG_KERNEL_ADVANCE) != 0;
-  const bool solo = (a->kernel & PG_KERNEL_SOLO) != 0;
-  pg_eval_args named = *a;
+  advance = (a->kernel & PG_KERNEL_ADVANCE) != 0;
+  solo = (a->kernel & PG_KERNEL_SOLO) != 0;
+  named = *a;
   named.kernel = a->kernel & 0xff;
+  rc = check_modifier_bits(named.kernel, advance, solo);
+  if (rc != PG_OK) return rc;
+  return scope_on_entry(named);
+}
+
+int32_t pg_eval_resolve(const pg_eval_args *a) {
+  pg_eval_args named;
+  bool advance, solo;
+  const int32_t rc = check_eval_entry(a, named, advance, solo);
+  if (rc != PG_OK) return rc;
+  const int kernel = resolve_kernel(&named);
+  return kernel | modifiers_in_effect(kernel, named, advance, solo);
+}
+
+int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
+  pg_eval_args named;
+  bool advance, solo;
+  int32_t rc = check_eval_entry(a, named, advance, solo);
+  if (rc != PG_OK) return rc;
   a = &named;
-  rc = check_modifier_bits(a->kernel, advance, solo);
-  if (rc != PG_OK) return rc;
-  rc = scope_on_entry(*a);
-  if (rc != PG_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (a->n_genomes == 0) {  // nothing to play (e.g. an empty shard); the counters still read zero
     if (a->counters) PG_HIP(hipMemsetAsync(a->counters, 0, 16 * sizeof(uint64_t), s));
@@ -587,7 +627,8 @@ int32_t pg_eval_population(const pg_eval_args *a, void *stream) {
     PG_HIP(hipMemsetAsync(a->workspace, 0, 256, s));
     if (a->counters) PG_HIP(hipMemsetAsync(a->counters, 0, 16 * sizeof(uint64_t), s));
   }  // the split kernel's k_prep_records zeroes the work header and the counters itself
-  rc = launch_games(kernel, a, p, advance, solo, s);
+  const int bits = modifiers_in_effect(kernel, *a, advance, solo);
+  rc = launch_games(kernel, a, p, (bits & PG_KERNEL_ADVANCE) != 0, (bits & PG_KERNEL_SOLO) != 0, s);
   if (rc != PG_OK) return rc;
   if (kernel == PG_KERNEL_SPLIT && a->prep == PG_PREP_GENOMES) return PG_OK;  // records only: no games, no fitness
   hipLaunchKernelGGL(k_fitness, dim3((a->n_genomes + 255) / 256), dim3(256), 0, s, a->rewards,

@@ -32,7 +32,8 @@ PG_KERNEL_RELU2 = 7
 PG_KERNEL_RELU_WIDE = 8
 PG_KERNEL_SIG2 = 9
 PG_KERNEL_ADVANCE = 0x100  # modifier bit of pg_eval_args.kernel: closed-form frame advance on RELU, RELU2, SIG2
-PG_KERNEL_SOLO = 0x800  # modifier bit of pg_eval_args.kernel: scripted-opponent games on half a lane group (the same three)
+PG_KERNEL_SOLO = 0x800  # modifier bit of pg_eval_args.kernel: scripted-opponent games on half a lane group (the same three,
+#                         and through AUTO k_service's [6, 33..64, O] layout: pg_eval_resolve tells where it applies)
 PG_STATE_FIELDS = 16
 STATE_FIELD_NAMES = ("ball_x", "ball_y", "ball_vx", "ball_vy", "ball_visible", "serve_timer",
                      "serve_dir", "hits", "point", "lpy", "rpy", "score1", "score2",
@@ -208,6 +209,7 @@ SIGNATURES = {
     "pg_eval_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PgEvalArgs)]),
     "pg_gene_count": (ctypes.c_int32, [ctypes.POINTER(PgNet)]),
     "pg_eval_population": (ctypes.c_int32, [ctypes.POINTER(PgEvalArgs), _vp]),
+    "pg_eval_resolve": (ctypes.c_int32, [ctypes.POINTER(PgEvalArgs)]),
     "pg_forward": (ctypes.c_int32, [ctypes.POINTER(PgForwardArgs), _vp]),
     "pg_decide": (ctypes.c_int32, [ctypes.POINTER(PgDecideArgs), _vp]),
     "pg_wide_decide_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(PgWideDecideArgs)]),

@@ -20,13 +20,18 @@ HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(C
 # the certified families' sources are compiled twice: with -DPG_SOLO_UNIT a unit
 # holds only the family's k_*_solo instances (PG_KERNEL_SOLO), so the first
 # object's kernels stay what they were and the two compile side by side
+# pg_service_solo.hip (k_service's solo instances) is compiled twice, as the base instances of its
+# layout are: the O = 3 ones under pong_ga.hip's scheduler flag, the O = 2 / 4 ones under the default
 # (object name, source, extra flags)
+_ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_general", "pg_general.hip", []), ("pg_ga", "pg_ga.hip", []),
          ("pg_hof_scan", "pg_hof_scan.cpp", []), ("pg_wide", "pg_wide.hip", []), ("pg_pixels", "pg_pixels.hip", []),
          ("pg_hof", "pg_hof.hip", []), ("pg_gen", "pg_gen.hip", []), ("pg_decide", "pg_decide.hip", []),
          ("pg_relu", "pg_relu.hip", []), ("pg_relu2", "pg_relu2.hip", []),
          ("pg_sig2", "pg_sig2.hip", []), ("pg_relu_solo", "pg_relu.hip", ["-DPG_SOLO_UNIT"]),
-         ("pg_relu2_solo", "pg_relu2.hip", ["-DPG_SOLO_UNIT"]), ("pg_sig2_solo", "pg_sig2.hip", ["-DPG_SOLO_UNIT"])] + [
+         ("pg_relu2_solo", "pg_relu2.hip", ["-DPG_SOLO_UNIT"]), ("pg_sig2_solo", "pg_sig2.hip", ["-DPG_SOLO_UNIT"]),
+         ("pg_service_solo", "pg_service_solo.hip", []),
+         ("pg_service_solo_o3", "pg_service_solo.hip", ["-DPG_SOLO_O3"] + _ILP)] + [
     (f"pg_service_more_L{L}_{f}", "pg_service_more.hip",
      [f"-DPG_MORE_L={L}", f"-DPG_MORE_F64={f}"] + (["-DPG_MORE_DISPATCH"] if (L, f) == (8, 1) else []))
     for L in (8, 16, 32, 64) for f in (1, 0)]
@@ -43,7 +48,6 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (pg_general.hip and pg_ga.hip hold kernels that were pong_ga.hip's: under the
 # flag they compile to what they were there; without it k_vary<float> differs
 # in 5 739 of its 5 963 lines)
-_ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
 SOURCE_FLAGS = {"pong_ga.hip": _ILP, "pg_general.hip": _ILP, "pg_ga.hip": _ILP}
 ARCH = os.environ.get("PG_OFFLOAD_ARCH", "gfx950")
 

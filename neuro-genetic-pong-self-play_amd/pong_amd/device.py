@@ -45,6 +45,15 @@ def kernel_code(name: str) -> int:
     return code
 
 
+def kernel_name(code: int) -> str:
+    """A pg_eval_resolve value in kernel_code's spelling: the kernel's name, then
+    "+advance" and "+solo" for the modifier bits in effect.  A reported name need
+    not be one kernel_code accepts: "split+solo" is what "auto+solo" runs on a
+    [6, 64, 3] sigmoid network."""
+    names = {v: k for k, v in KERNELS.items() if "+" not in k}
+    return names[code & 0xff] + "".join("+" + m for m, bit in MODIFIERS.items() if code & bit)
+
+
 def gene_count(nodes, bias=True) -> int:
     """utils.calculate_gene_size (utils.py:128-136) for an arbitrary shape."""
     b = 1 if bias else 0
@@ -264,6 +273,32 @@ class Evaluator:
         self._prep_key = self._prep_of(genomes, rows, n_active, n) if prep == "genomes" else None
         self._prep_ws = ws.data_ptr() if prep == "genomes" else None
         return out, trace
+
+    def resolved_kernel(self, kernel: Optional[str] = None, traced: bool = False, hard_log: bool = False,
+                        horizon: Optional[int] = None, group_lanes: Optional[int] = None,
+                        precision: Optional[str] = None) -> str:
+        """The kernel an evaluate() call with these settings runs, "auto" resolved and
+        with the modifiers that take effect on it (pg_eval_resolve; ``kernel_name``'s
+        spelling, e.g. "split+solo", "split", "relu+advance+solo", "general").  Host
+        only: nothing is launched.  ``traced`` / ``hard_log``: the call passes
+        trace_games and trace_cap / a hard_log tensor.  Raises PongGAError where
+        evaluate() would refuse the settings on entry."""
+        a = L.PgEvalArgs()
+        a.net = self.net
+        a.n_genomes, a.n_games = 1, self.n_games
+        a.precision = PRECISIONS[precision or self.precision]
+        a.kernel = kernel_code(kernel or self.kernel)
+        a.group_lanes = self.group_lanes if group_lanes is None else int(group_lanes)
+        a.horizon = self.horizon if horizon is None else int(horizon)
+        a.timeout_thresh, a.win_score = self.timeout_thresh, self.win_score
+        if traced:  # (never followed: pg_eval_resolve reads whether they are set)
+            a.trace, a.trace_games, a.trace_cap = ctypes.c_void_p(1), 1, 1
+        if hard_log:
+            a.hard_log, a.hard_cap = ctypes.c_void_p(1), 1
+        code = L.lib().pg_eval_resolve(ctypes.byref(a))
+        if code < 0:
+            L.check("pg_eval_resolve", code)
+        return kernel_name(code)
 
     @staticmethod
     def _prep_of(genomes, rows, n_active, n):

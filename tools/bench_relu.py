@@ -22,6 +22,8 @@ interquartile range) of >= 20 launches are reported.
     python tools/bench_relu.py --schedule reference --runs relu:4096 relu+solo:4096 relu:4096 relu+solo:4096
         # scripted-opponent games on half a lane group against the base kernel; relu2+solo,
         # sig2+solo and X+advance+solo against X+advance alike
+    python tools/bench_relu.py --activation sigmoid --schedule reference \
+        --runs auto:65536 auto+solo:65536 auto:65536 auto+solo:65536              # k_service's solo instance (4.2j)
 
 --schedule: selfplay (the default: every game against a hall member), reference
 (evaluate()'s kinds [0,1,2,3,3,3] per genome, the NN games against the same
@@ -72,10 +74,13 @@ def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64, g
 
 
 KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu_wide": "k_wide<relu>", "general": "k_general",
-                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide"}
+                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide", "auto": "auto"}
 FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid",
                     "wide": "sigmoid"}
-MODIFIED = ("relu", "relu2", "sig2")  # the families "+advance" and "+solo" go with (pong_amd.device.kernel_code)
+# the names "+advance" and "+solo" go with (pong_amd.device.kernel_code); auto runs the network of --activation on
+# what PG_KERNEL_AUTO picks and reports it as Evaluator.resolved_kernel does: "auto+solo" with --activation sigmoid
+# --shape 6 64 3 is k_service's solo instance
+MODIFIED = ("relu", "relu2", "sig2", "auto")
 SCHEDULES = {"selfplay": None, "reference": [0, 1, 2, 3, 3, 3], "scripted": [0, 1, 2, 0, 0, 0]}
 
 
@@ -125,6 +130,8 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
     if keep is not None:  # the timed inputs' results, for the untimed X against X+solo comparison
         keep[(base, mods, pop)] = [getattr(res, f).clone() for f in ("fitness", "rewards", "scores", "frames")]
     kernel_name = KERNEL_NAMES[base] + ("_adv" if "advance" in mods else "") + ("_solo" if "solo" in mods else "")
+    if base == "auto":
+        kernel_name = "auto: " + ev.resolved_kernel()
     out = {"kernel": kernel_name, "schedule": "selfplay" if kinds is None else kinds, "genome_dtype": str(dtype).replace("torch.", ""),
             "activation": activation, "shape": list(shape), "pop": pop, "games": 6, "hall": int(hall.shape[0]) if hall is not None else 0,
             "launches": launches, "warmup": warmup,
@@ -150,8 +157,9 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service, "
-                   "relu+advance, relu2+advance, sig2+advance, and relu, relu2, sig2 with +solo or +advance+solo")
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service, auto, "
+                   "relu+advance, relu2+advance, sig2+advance, auto+advance, and relu, relu2, sig2, auto with +solo or "
+                   "+advance+solo")
     p.add_argument("--schedule", default="selfplay", choices=sorted(SCHEDULES),
                    help="the games' kinds per genome: selfplay (all against the hall), reference ([0,1,2,3,3,3]) or "
                    "scripted (generation 0: [0,1,2,0,0,0], no hall)")

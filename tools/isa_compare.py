@@ -7,7 +7,12 @@ moves with the kernel's place in its code object, not with its code.  The
 s_nop padding after a kernel's last instruction is dropped.  Prints
 every difference and a summary line; exits 1 if there is any.
 
-    python tools/isa_compare.py OLD.so NEW.so
+    python tools/isa_compare.py OLD.so NEW.so [--rename REGEX=REPLACEMENT]
+
+--rename rewrites OLD's kernel symbols before they are matched, for a change
+that adds a defaulted template parameter to a kernel and so renames every
+instance without touching its code: k_service's kSolo is
+    --rename '(_ZN2pg9k_serviceI\w+?)EEvNS_=\1Lb0EEEvNS_'
 """
 import os
 import re
@@ -58,6 +63,11 @@ def build(lib):
 
 def main(argv):
     (rows_a, code_a), (rows_b, code_b) = build(argv[0]), build(argv[1])
+    if "--rename" in argv:
+        pattern, repl = argv[argv.index("--rename") + 1].split("=", 1)
+        rows_a = {re.sub(pattern, repl, name): dict(row, name=re.sub(pattern, repl, row["name"]))
+                  for name, row in rows_a.items()}
+        code_a = {re.sub(pattern, repl, name): lines for name, lines in code_a.items()}
     diffs = 0
     for name in sorted(set(rows_a) ^ set(rows_b)):
         diffs += 1

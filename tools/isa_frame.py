@@ -12,7 +12,12 @@ k_service<8,16,3,double,untraced,no-horizon> and reports
   * every scratch (spill) instruction of the kernel by source line: where the
     register allocator spilled, so that none sits on the common path.
 
-    python tools/isa_frame.py [-DNAME ...] [--dump listing.txt] [> profiles/r05/isa_frame.txt]
+    python tools/isa_frame.py [--solo [O [double|float]]] [-DNAME ...] [--dump listing.txt] [> profiles/r05/isa_frame.txt]
+
+--solo: a kSolo instance of the same layout instead (pg_service_solo.hip,
+DESIGN.md 4.2j), O = 3 and double unless given: O = 3 from the -DPG_SOLO_O3
+unit under the iterative-ILP scheduler, O = 2 and 4 from the other unit under
+the default one, as pong_amd/build.py compiles them.
 """
 import collections
 import os
@@ -23,18 +28,20 @@ import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "neuro-genetic-pong-self-play_amd", "csrc")
-SYM = "_ZN2pg9k_serviceILi8ELi16ELi3EdLb1ELb0EEEvNS_10EvalParamsE"
+SYM = "_ZN2pg9k_serviceILi8ELi16ELi3EdLb1ELb0ELb0EEEvNS_10EvalParamsE"
+SOLO_SYM = "_ZN2pg9k_serviceILi8ELi16ELi{O}E{t}Lb1ELb0ELb1EEEvNS_10EvalParamsE"  # t: d or f
 HIPCC = "/opt/rocm/bin/hipcc"
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
-def disassemble(tmp, defs=()):
+def disassemble(tmp, defs=(), sym=SYM, source="pong_ga.hip", ilp=True):
     obj = os.path.join(tmp, "k.o")
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                           "-fno-slp-vectorize", "-I", os.path.join(REPO, "include"), "-mllvm",
-                           "-amdgpu-sched-strategy=iterative-ilp", "-gline-tables-only", "--cuda-device-only",
-                           "--no-gpu-bundle-output", *defs, "-c", "-o", obj, os.path.join(CSRC, "pong_ga.hip")])
-    out = subprocess.check_output([OBJDUMP, "-d", "-l", "--no-show-raw-insn", "--disassemble-symbols=" + SYM, obj],
+                           "-fno-slp-vectorize", "-I", os.path.join(REPO, "include"),
+                           *(["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] if ilp else []),
+                           "-gline-tables-only", "--cuda-device-only",
+                           "--no-gpu-bundle-output", *defs, "-c", "-o", obj, os.path.join(CSRC, source)])
+    out = subprocess.check_output([OBJDUMP, "-d", "-l", "--no-show-raw-insn", "--disassemble-symbols=" + sym, obj],
                                   text=True)
     rows, cur = [], "?"
     for ln in out.splitlines():
@@ -79,8 +86,17 @@ def main():
         if a == "-mllvm" and i + 1 < len(sys.argv):
             defs += [a, sys.argv[i + 1]]
     dump = sys.argv[sys.argv.index("--dump") + 1] if "--dump" in sys.argv else None
+    solo, sym = "--solo" in sys.argv, SYM
+    if solo:
+        rest = sys.argv[sys.argv.index("--solo") + 1:]
+        outs = int(rest[0]) if rest and rest[0] in ("2", "3", "4") else 3
+        gene = rest[1] if len(rest) > 1 and rest[1] in ("double", "float") else "double"
+        sym = SOLO_SYM.format(O=outs, t=gene[0])
     with tempfile.TemporaryDirectory() as tmp:
-        rows = disassemble(tmp, defs)
+        if solo:
+            rows = disassemble(tmp, defs + (["-DPG_SOLO_O3"] if outs == 3 else []), sym, "pg_service_solo.hip", outs == 3)
+        else:
+            rows = disassemble(tmp, defs)
     if dump:
         with open(dump, "w") as fh:
             for a, src, ins in rows:
@@ -107,7 +123,7 @@ def main():
         if k.startswith("valu"):
             files[src.split(":")[0]] += 1
         scratch_hot += ins.startswith("scratch_")
-    print(f"# {SYM}: common frame path 0x{start:x}..0x{end:x} (one wave-frame, 8 games)")
+    print(f"# {sym}: common frame path 0x{start:x}..0x{end:x} (one wave-frame, 8 games)")
     for k in ("valu", "valu (transcendental)", "salu", "lds", "memory"):
         print(f"  {k:24s} {c[k]}")
     print(f"  VALU total               {c['valu'] + c['valu (transcendental)']}")
