@@ -32,6 +32,7 @@
  * pg_relu_decide                 the same, as k_relu decides it (ReLU networks: numpy_nn.py:6-9,
  *                                the "alternative activation function" of numpy_nn.py:26)
  * pg_relu2_decide                the same, as k_relu2 decides it (ReLU networks with two hidden layers)
+ * pg_relu2_block_decide          the same, as k_relu2_block decides it (two hidden layers of up to 128 units)
  * pg_relu_wide_decide            the same, as k_wide's ReLU instances decide it (wide ReLU networks)
  * pg_sig2_decide                 the same, as k_sig2 decides it (sigmoid networks with two hidden layers)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
@@ -114,7 +115,7 @@ typedef enum pg_precision {
 typedef enum pg_kernel {
   PG_KERNEL_AUTO = 0,      /* SPLIT when the shape and precision allow, else GENERAL (ReLU nets: RELU or RELU2
                               in their scopes; every ReLU net outside them runs on GENERAL under AUTO --
-                              RELU_WIDE is never picked by AUTO, it is chosen explicitly).  AUTO never sets a
+                              RELU_WIDE and RELU2_BLOCK are never picked by AUTO, they are chosen explicitly).  AUTO never sets a
                               modifier bit itself; one OR-ed in takes effect where the kernel it picks has the
                               instance (PG_KERNEL_SOLO below), and pg_eval_resolve reports what a call runs */
   PG_KERNEL_GENERAL = 1,   /* one wave per game, f64, any NETWORK_SHAPE */
@@ -152,7 +153,17 @@ typedef enum pg_kernel {
                               the rest recomputed in f64 in numpy's order.  Every frame is
                               stepped (counters [8] = [12] = 0) unless PG_KERNEL_ADVANCE is set; no lane records, no workspace beyond the
                               base.  PG_ERR_UNSUPPORTED for a ReLU net, any other shape, no bias, PG_PREC_F64,
-                              horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it */
+                              horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it */,
+  PG_KERNEL_RELU2_BLOCK = 10 /* PG_ACT_RELU only: [6, 2<=H1<=128, 2<=H2<=128, 2..4] with bias, certified precision,
+                                f32 or f64 genomes, every opponent kind, whole episodes: k_relu2's certificate and
+                                f64 re-decision one level up -- one 256-thread block plays a game,
+                                128 threads per paddle's network, a whole W2 row as f32 in each thread's
+                                registers for the game, layer 1 all-gathered through LDS behind a barrier each
+                                frame.  Every frame is stepped (counters [8] = [12] = 0); no lane records, no
+                                workspace beyond the base.  PG_ERR_UNSUPPORTED for a sigmoid net, any other shape,
+                                no bias, PG_PREC_F64, horizon > 0 and hard_log, and with PG_KERNEL_ADVANCE or
+                                PG_KERNEL_SOLO.  Chosen explicitly only: AUTO never picks it (it runs such
+                                networks on GENERAL) */
 } pg_kernel;
 
 /* pg_eval_args.kernel holds a pg_kernel in its low byte and modifier bits above it (ABI 13).
@@ -167,8 +178,8 @@ enum {
                                and hard_log stay refused); the workspace is the same.  PG_KERNEL_AUTO with the
                                bit resolves exactly as without it: where it picks RELU or RELU2 the advance is
                                on, where it picks SPLIT, WIDE or GENERAL the bit changes nothing.  Every other
-                               explicit kernel with the bit: PG_ERR_UNSUPPORTED (checked, like the bits, even
-                               for an empty launch).  A launch with trace != NULL records every frame and so
+                               explicit kernel with the bit (PG_KERNEL_RELU2_BLOCK among them): PG_ERR_UNSUPPORTED
+                               (checked, like the bits, even for an empty launch).  A launch with trace != NULL records every frame and so
                                runs with the advance off, which is not an error ([8] = [12] = 0) */,
   PG_KERNEL_SOLO = 0x800    /* scripted-opponent games on half a lane group, opt-in: PG_KERNEL_RELU,
                                PG_KERNEL_RELU2 and PG_KERNEL_SIG2 give every game a group of 2 LN lanes, of which
@@ -215,7 +226,7 @@ typedef struct pg_net {
   int32_t bias;                  /* 1 = BIAS, weight rows are (in + 1) wide */
   int32_t dtype;                 /* pg_dtype of genomes and opponents */
   int32_t activation;            /* ABI 13: pg_activation; 0 (a zero-initialised net) = the sigmoid.  ReLU
-                                    networks run on PG_KERNEL_RELU / PG_KERNEL_RELU2 / PG_KERNEL_RELU_WIDE / PG_KERNEL_GENERAL and pg_forward (always
+                                    networks run on PG_KERNEL_RELU / PG_KERNEL_RELU2 / PG_KERNEL_RELU2_BLOCK / PG_KERNEL_RELU_WIDE / PG_KERNEL_GENERAL and pg_forward (always
                                     f64) only: pg_decide, pg_wide_decide, PG_KERNEL_SPLIT, PG_KERNEL_WIDE,
                                     horizon > 0 and hard_log return PG_ERR_UNSUPPORTED for them */
 } pg_net;
@@ -256,7 +267,8 @@ typedef struct pg_eval_args {
                                     timeout at once; [9] hard decisions (see hard_log); split kernel:
                                     [12] serve-delay frames advanced at once (ball hidden); the
                                     episodes' frames = [0] + [8] + [12]; [10], [11], [13..15] 0.
-                                    RELU, RELU2 and SIG2 step every frame ([8] = [12] = 0) unless
+                                    RELU2_BLOCK steps every frame ([8] = [12] = 0); so do
+                                    RELU, RELU2 and SIG2 unless
                                     PG_KERNEL_ADVANCE is set on an untraced launch: then [8] and [12]
                                     count as for the split kernel, [0] the stepped frames only, and
                                     [1], [2], [4] only the forwards actually run */
@@ -611,6 +623,10 @@ int32_t pg_relu_decide(const pg_relu_decide_args *args, void *stream);
 /* The same for k_relu2 (PG_KERNEL_RELU2): [6, 2..64, 2..64, 2..4] ReLU networks with bias; z32 is
  * [n, nodes[3]].  The decision code of a k_relu2 frame on given inputs. */
 int32_t pg_relu2_decide(const pg_relu_decide_args *args, void *stream);
+/* The same for k_relu2_block (PG_KERNEL_RELU2_BLOCK): [6, 2..128, 2..128, 2..4] ReLU networks with bias;
+ * index, stage (0 certified, 1 f64), z32 [n, nodes[3]] and bound as pg_relu2_decide's.  The decision code
+ * of a k_relu2_block frame on given inputs, one block per pass. */
+int32_t pg_relu2_block_decide(const pg_relu_decide_args *args, void *stream);
 /* The decision code of a k_sig2 frame (PG_KERNEL_SIG2) on given inputs: PG_ACT_SIGMOID networks
  * [6, 2..64, 2..64, 2..4] with bias, the argument struct of pg_relu_decide.  index [n]: the argmax of
  * numpy's f64 sigmoid outputs; stage [n]: 0 the f32 certificate (certify_c under the network's static

@@ -75,7 +75,11 @@ ACTIVATION = "sigmoid"
 # leaves on the general kernel; "sig2" is the opt-in certified f32 kernel for
 # two-hidden-layer sigmoid networks (ACTIVATION = "sigmoid", NETWORK_SHAPE
 # [6, 2..64, 2..64, 2..4], BIAS), which "auto" leaves on the general kernel (on
-# the wide one from 64 units up); a kernel that cannot run the configured
+# the wide one from 64 units up); "relu2_block" is the opt-in certified f32
+# kernel for two-hidden-layer ReLU networks of up to 128 units a layer
+# (ACTIVATION = "relu", NETWORK_SHAPE [6, 2..128, 2..128, 2..4], BIAS), which
+# "auto" leaves on the general kernel above 64 units (it takes
+# no "+advance" or "+solo"); a kernel that cannot run the configured
 # network is an error, never a fallback.  "relu+advance", "relu2+advance",
 # "sig2+advance" and "auto+advance" are the opt-in closed-form frame advance of
 # the certified f32 kernels (serve delays and periodic rallies are not stepped

@@ -11,6 +11,7 @@
 //   pg_general.hip       the f64 path: k_general, pg_forward with k_forward_general
 //   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
 //   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
+//   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate with a block per game (widths up to 128)
 //   pg_decide.hip        k_decide (pg_decide)
 //   pg_ga.hip            selection, variation, schedule, row gather and hash
 //   pg_gen.hip, pg_hof.hip, pg_pixels.hip    the generation's device steps, the
@@ -224,6 +225,12 @@ int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hip
 bool relu2_shape_ok(const pg_net &n);
 int32_t relu2_scope(const pg_eval_args &a);
 int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
+
+// [6, 2..128, 2..128, 2..4] ReLU networks with bias on k_relu2_block (pg_relu2_block.hip): k_relu2's
+// certificate with a 256-thread block per game; certified precision, no workspace beyond the base, no
+// horizon, no hard-case log, no modifier bits
+int32_t relu2_block_scope(const pg_eval_args &a);
+int32_t launch_relu2_block(const EvalParams &p, int dtype, hipStream_t s);
 
 // [6, 2..64, 2..64, 2..4] sigmoid networks with bias on k_sig2 (pg_sig2.hip, pg_hidden2.hpp)
 int32_t sig2_scope(const pg_eval_args &a);

@@ -27,19 +27,23 @@ ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 # families play a game against a scripted opponent on half a lane group, with the same results
 MODIFIERS = {"advance": L.PG_KERNEL_ADVANCE, "solo": L.PG_KERNEL_SOLO}
 MODIFIED = ("relu", "relu2", "sig2", "auto")  # the bases either modifier goes with
+# kernels chosen by name only, without modifiers: kernel_code and kernel_name consult this mapping after KERNELS
+MORE_KERNELS = {"relu2_block": L.PG_KERNEL_RELU2_BLOCK}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
 
 def kernel_code(name: str) -> int:
-    """pg_eval_args.kernel for a kernel name: a key of ``KERNELS`` without "+",
-    optionally followed by "+advance" and "+solo" in either order, each at most
-    once and only on relu, relu2, sig2 and auto (KeyError otherwise)."""
+    """pg_eval_args.kernel for a kernel name: a key of ``KERNELS`` without "+"
+    or of ``MORE_KERNELS``, optionally followed by "+advance" and "+solo" in
+    either order, each at most once and only on relu, relu2, sig2 and auto
+    (KeyError otherwise)."""
     base, *mods = str(name).split("+")
-    ok = base in KERNELS and (not mods or base in MODIFIED) and len(set(mods)) == len(mods)
+    known = {**KERNELS, **MORE_KERNELS}
+    ok = base in known and (not mods or base in MODIFIED) and len(set(mods)) == len(mods)
     if not ok or any(m not in MODIFIERS for m in mods):
-        raise KeyError(f"kernel {name!r}: valid are {sorted(k for k in KERNELS if '+' not in k)}, and "
+        raise KeyError(f"kernel {name!r}: valid are {sorted(k for k in known if '+' not in k)}, and "
                        f"{list(MODIFIED)} with '+advance' and/or '+solo' (e.g. 'auto+advance+solo')")
-    code = KERNELS[base]
+    code = known[base]
     for m in mods:
         code |= MODIFIERS[m]
     return code
@@ -50,7 +54,7 @@ def kernel_name(code: int) -> str:
     "+advance" and "+solo" for the modifier bits in effect.  A reported name need
     not be one kernel_code accepts: "split+solo" is what "auto+solo" runs on a
     [6, 64, 3] sigmoid network."""
-    names = {v: k for k, v in KERNELS.items() if "+" not in k}
+    names = {v: k for k, v in {**KERNELS, **MORE_KERNELS}.items() if "+" not in k}
     return names[code & 0xff] + "".join("+" + m for m, bit in MODIFIERS.items() if code & bit)
 
 
@@ -385,6 +389,11 @@ class Evaluator:
         """The same for the two-hidden-layer ReLU kernel (pg_relu2_decide:
         k_relu2's decision code, [6, 2..64, 2..64, 2..4] networks with bias)."""
         return self._relu_decide("pg_relu2_decide", genomes, k, genome_index)
+
+    def relu2_block_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The same for the block-per-game ReLU kernel (pg_relu2_block_decide:
+        k_relu2_block's decision code, [6, 2..128, 2..128, 2..4] networks with bias)."""
+        return self._relu_decide("pg_relu2_block_decide", genomes, k, genome_index)
 
     def sig2_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
         """The two-hidden-layer sigmoid kernel's own decision (pg_sig2_decide:

@@ -13,6 +13,8 @@ interquartile range) of >= 20 launches are reported.
     python tools/bench_relu.py                      # the four runs
     python tools/bench_relu.py --runs relu:4096 general:4096 --launches 30
     python tools/bench_relu.py --shape 6 64 64 3 --runs relu2:4096 general:4096   # k_relu2
+    python tools/bench_relu.py --shape 6 128 128 3 --dtype float32 --launches 5 \
+        --runs relu2_block:4096 relu_wide:4096 general:4096   # k_relu2_block
     python tools/bench_relu.py --shape 6 512 512 3 --dtype float32 --launches 5 \
         --runs relu_wide:4096 general:4096                                        # k_wide's ReLU instances (4.2e)
     python tools/bench_relu.py --shape 6 64 64 3 --activation sigmoid \
@@ -35,7 +37,7 @@ Every run reports rally_share and serve_delay_share: counters [8] and [12] as
 shares of the episode frames (0 for a kernel that steps every frame).
 
 --activation sets the activation of the general and wide runs (default relu;
-relu, relu2 and relu_wide runs are always ReLU, sig2 and service runs always
+relu, relu2, relu2_block and relu_wide runs are always ReLU, sig2 and service runs always
 sigmoid).  --genes uniform draws U[0, 1) genes (generation 0 of a reference
 run, ga.py:85) instead of N(0, 3).
 
@@ -73,9 +75,9 @@ def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64, g
     return genomes, hall
 
 
-KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu_wide": "k_wide<relu>", "general": "k_general",
+KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu2_block": "k_relu2_block", "relu_wide": "k_wide<relu>", "general": "k_general",
                 "service": "k_service", "sig2": "k_sig2", "wide": "k_wide", "auto": "auto"}
-FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid",
+FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu2_block": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid",
                     "wide": "sigmoid"}
 # the names "+advance" and "+solo" go with (pong_amd.device.kernel_code); auto runs the network of --activation on
 # what PG_KERNEL_AUTO picks and reports it as Evaluator.resolved_kernel does: "auto+solo" with --activation sigmoid
@@ -157,7 +159,7 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu_wide, sig2, wide, general, service, auto, "
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu2_block, relu_wide, sig2, wide, general, service, auto, "
                    "relu+advance, relu2+advance, sig2+advance, auto+advance, and relu, relu2, sig2, auto with +solo or "
                    "+advance+solo")
     p.add_argument("--schedule", default="selfplay", choices=sorted(SCHEDULES),
@@ -166,14 +168,19 @@ def main():
     p.add_argument("--shape", nargs="+", type=int, default=SHAPE,
                    help="NETWORK_SHAPE (default 6 64 3; relu2 needs two hidden layers, e.g. 6 64 64 3)")
     p.add_argument("--warmup", type=int, default=3)
-    p.add_argument("--launches", type=int, default=20, help="timed launches (>= 20; >= 5 for layers wider than 256)")
+    p.add_argument("--launches", type=int, default=20, help="timed launches (>= 20; >= 5 for layers wider than 256, or wider than 64 with general, relu_wide or wide among the runs)")
     p.add_argument("--dtype", default="float64", choices=["float64", "float32"], help="genome storage type")
     p.add_argument("--activation", default="relu", choices=["relu", "sigmoid"],
                    help="activation of the general runs (the other kernels have one activation each)")
     p.add_argument("--genes", default="normal", choices=["normal", "uniform"], help="N(0, 3) genes or U[0, 1)")
     args = p.parse_args()
-    if args.launches < (5 if max(args.shape[1:-1]) > 256 else 20):
-        p.error("--launches must be >= 20 (>= 5 for layers wider than 256: seconds per launch)")
+    # seconds per launch: any kernel above 256 units a layer; above 64, the general and the wide kernels
+    bases = {spec.split(":")[0].split("+")[0] for spec in args.runs}
+    width = max(args.shape[1:-1])
+    slow = width > 256 or (width > 64 and bases & {"general", "relu_wide", "wide"})
+    if args.launches < (5 if slow else 20):
+        p.error("--launches must be >= 20 (>= 5 for layers wider than 256, and for layers wider than 64 when the "
+                "runs hold general, relu_wide or wide: seconds per launch)")
     dev = torch.device("cuda", torch.cuda.current_device())
     keep = {}
     for spec in args.runs:
