@@ -19,6 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liboracle.so")
 
 OPP_HARDCODED, OPP_ROM_CPU, OPP_SCORE, OPP_NN = 0, 1, 2, 3
+ACTIVATIONS = {"sigmoid": 0, "relu": 1}  # or_net.activation (OR_ACT_*; pg_net.activation, PG_ACT_*)
 
 _lib = None
 
@@ -46,7 +47,7 @@ class OrState(ctypes.Structure):
 
 class OrNet(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int), ("nodes", ctypes.POINTER(ctypes.c_int)),
-                ("bias", ctypes.c_int)]
+                ("bias", ctypes.c_int), ("activation", ctypes.c_int)]
 
 
 class OrGameResult(ctypes.Structure):
@@ -108,11 +109,14 @@ def _ip(a):
 class Net:
     """Keeps the ctypes network descriptor and its node array alive."""
 
-    def __init__(self, nodes, bias=True):
+    def __init__(self, nodes, bias=True, activation="sigmoid"):
+        if activation not in ACTIVATIONS:
+            raise ValueError("activation must be 'sigmoid' or 'relu', not %r" % (activation,))
         self.nodes_arr = (ctypes.c_int * len(nodes))(*[int(n) for n in nodes])
-        self.s = OrNet(len(nodes), self.nodes_arr, 1 if bias else 0)
+        self.s = OrNet(len(nodes), self.nodes_arr, 1 if bias else 0, ACTIVATIONS[activation])
         self.nodes = list(nodes)
         self.bias = bool(bias)
+        self.activation = activation
 
     @property
     def ref(self):
@@ -130,9 +134,10 @@ def game_seed(base_seed: int, game_index: int) -> int:
     return lib().or_game_seed(base_seed, game_index)
 
 
-def nn_run(genes, nodes, x, bias=True):
-    """numpy_nn.NeuralNetwork.run restated: returns (argmax index, final activations)."""
-    net = Net(nodes, bias)
+def nn_run(genes, nodes, x, bias=True, activation="sigmoid"):
+    """numpy_nn.NeuralNetwork.run restated: returns (argmax index, final activations).
+    ``activation``: config.py's ACTIVATION, "sigmoid" or "relu" (np.maximum(0.0, x))."""
+    net = Net(nodes, bias, activation)
     g = np.ascontiguousarray(genes, dtype=np.float64)
     xx = np.ascontiguousarray(x, dtype=np.float64)
     out = np.zeros(nodes[-1], dtype=np.float64)
@@ -191,15 +196,15 @@ class limits:
 
 
 def play_game(genes, nodes, opp_kind, opp_genes=None, mult=1.0, seed=0, bias=True, trace_cap=0, horizon=0,
-              timeout_thresh=0, win_score=0):
+              timeout_thresh=0, win_score=0, activation="sigmoid"):
     """One game slot (or_play_slot): a perform_episode, or with ``horizon`` > 0
     the fixed-horizon mode (T frames, auto-reset; pong_ga.h pg_eval_args.horizon)."""
     with limits(timeout_thresh, win_score):
-        return _play_game(genes, nodes, opp_kind, opp_genes, mult, seed, bias, trace_cap, horizon)
+        return _play_game(genes, nodes, opp_kind, opp_genes, mult, seed, bias, trace_cap, horizon, activation)
 
 
-def _play_game(genes, nodes, opp_kind, opp_genes, mult, seed, bias, trace_cap, horizon):
-    net = Net(nodes, bias)
+def _play_game(genes, nodes, opp_kind, opp_genes, mult, seed, bias, trace_cap, horizon, activation="sigmoid"):
+    net = Net(nodes, bias, activation)
     g = np.ascontiguousarray(genes, dtype=np.float64)
     og = np.ascontiguousarray(opp_genes, dtype=np.float64) if opp_genes is not None else None
     res = OrGameResult()
@@ -213,17 +218,19 @@ def _play_game(genes, nodes, opp_kind, opp_genes, mult, seed, bias, trace_cap, h
 
 
 def eval_population(genomes, nodes, kind, opp_index, mult, opponents=None, bias=True,
-                    base_seed=0, n_threads=0, horizon=0, timeout_thresh=0, win_score=0):
+                    base_seed=0, n_threads=0, horizon=0, timeout_thresh=0, win_score=0, activation="sigmoid"):
     """Whole-population evaluate(): returns a dict of numpy arrays (``horizon`` > 0:
     every game slot in the fixed-horizon mode, or_eval_population_h; ``timeout_thresh``,
-    ``win_score``: config.py's TIMEOUT_THRESH / WIN_SCORE, 0 = the reference's)."""
+    ``win_score``: config.py's TIMEOUT_THRESH / WIN_SCORE, 0 = the reference's;
+    ``activation``: config.py's ACTIVATION, "sigmoid" or "relu")."""
     with limits(timeout_thresh, win_score):
         return _eval_population(genomes, nodes, kind, opp_index, mult, opponents, bias, base_seed, n_threads,
-                                horizon)
+                                horizon, activation)
 
 
-def _eval_population(genomes, nodes, kind, opp_index, mult, opponents, bias, base_seed, n_threads, horizon):
-    net = Net(nodes, bias)
+def _eval_population(genomes, nodes, kind, opp_index, mult, opponents, bias, base_seed, n_threads, horizon,
+                     activation="sigmoid"):
+    net = Net(nodes, bias, activation)
     G = np.ascontiguousarray(genomes, dtype=np.float64)
     n = G.shape[0]
     kind = np.ascontiguousarray(kind, dtype=np.int32)

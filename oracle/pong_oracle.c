@@ -270,6 +270,7 @@ int or_nn_run(const double *genes, const or_net *net, const double *x, double *o
   double *cur = buf0, *nxt = buf1;
   const int b = net->bias ? 1 : 0;
   const int n_in = net->nodes[0];
+  const int relu = net->activation == OR_ACT_RELU;
   for (int i = 0; i < n_in; ++i) cur[i] = x[i];
   if (b) cur[n_in] = 1.0;
   long off = 0;
@@ -278,7 +279,10 @@ int or_nn_run(const double *genes, const or_net *net, const double *x, double *o
     for (int j = 0; j < nout; ++j) {
       const double *w = genes + off + (long)j * cols; /* row-major (out, in+bias) numpy_nn.py:63 */
       const double z = or_blas_dot(w, cur, cols, j, nout); /* np.dot(w, column), numpy_nn.py:127 */
-      nxt[j] = 1.0 / (1.0 + pow(M_E, -z)); /* 1 / (1 + np.e ** -x), numpy_nn.py:22-23 */
+      if (relu) /* np.maximum(0.0, x), numpy_nn.py:6-9: a NaN stays NaN, -0.0 and -inf give 0.0 */
+        nxt[j] = !(z <= 0.0) ? z : 0.0;
+      else
+        nxt[j] = 1.0 / (1.0 + pow(M_E, -z)); /* 1 / (1 + np.e ** -x), numpy_nn.py:22-23 */
     }
     if (b) nxt[nout] = 1.0;
     off += (long)cols * nout;

@@ -7,8 +7,11 @@
  *
  * It is a plain-C restatement of the reference's per-genome evaluation
  * (n00b001/neuro-genetic-pong-self-play):
- *   - NeuralNetwork.run            numpy_nn.py:120-137  (f64, sigmoid = 1/(1+e**-x) numpy_nn.py:22-23;
- *                                  np.dot in OpenBLAS dgemv_t's order, or_blas_dot)
+ *   - NeuralNetwork.run            numpy_nn.py:120-137  (f64, np.dot in OpenBLAS dgemv_t's order,
+ *                                  or_blas_dot; the activation in every layer, the last included,
+ *                                  numpy_nn.py:126-129, chosen by or_net.activation:
+ *                                  sigmoid = 1/(1+e**-x) numpy_nn.py:22-23, or
+ *                                  relu = np.maximum(0.0, x) numpy_nn.py:6-9, which keeps a NaN)
  *   - populate_weights layout      numpy_nn.py:52-69
  *   - inference features           utils.py:139-153
  *   - get_actions                  main.py:138-154
@@ -76,10 +79,14 @@ typedef struct {
   uint64_t seed;
 } or_pong_state;
 
+/* activations of or_net (numpy_nn.py:6-9, 22-23) */
+enum { OR_ACT_SIGMOID = 0, OR_ACT_RELU = 1 };
+
 typedef struct {
   int n_nodes;        /* len(NETWORK_SHAPE) */
   const int *nodes;   /* NETWORK_SHAPE; nodes[0] must be 6 for the game loop */
   int bias;           /* BIAS */
+  int activation;     /* ACTIVATION: OR_ACT_SIGMOID or OR_ACT_RELU (pg_net.activation, PG_ACT_*) */
 } or_net;
 
 typedef struct {
@@ -101,7 +108,10 @@ int or_env_done(const or_pong_state *s);
 
 int or_gene_count(const or_net *net);
 /* numpy_nn.NeuralNetwork.run: returns argmax index; writes the final-layer
- * activations (len nodes[last]) into out_act if non-NULL. */
+ * activations (len nodes[last]) into out_act if non-NULL.  With OR_ACT_RELU a
+ * NaN pre-activation stays NaN (np.maximum propagates it, np.argmax returns the
+ * first), -inf becomes 0, +inf stays, and outputs that are all <= 0 tie at 0,
+ * so index 0 wins. */
 /* np.dot(W, x) for a C-contiguous [n, m] float64 W, in the operation order of
  * numpy's OpenBLAS dgemv_t (x86-64 AVX2/FMA kernel); see pong_oracle.c. */
 double or_blas_dot(const double *a, const double *x, int m, int j, int n);

@@ -16,9 +16,11 @@ BOUND_HDR = os.path.join(REPO, "neuro-genetic-pong-self-play_amd", "csrc", "pg_r
 RELU2_K = 87.0  # PG_RELU2_K = 9 + 65 + 11 + 2
 
 # the issue's shapes, plus [6, 32, 17, 2] and [6, 20, 32, 4]: the 16-lane instance (widths 17..32), which none of
-# the issue's shapes reaches, with padding in either layer
+# the issue's shapes reaches, with padding in either layer; [6, 16, 16, 4] and [6, 32, 32, 3] complete the
+# (lane layout, outputs) cells: the 4-lane layout with 4 outputs and the 16-lane layout with 3 (tests/_sig2_model.py
+# imports this list, so k_sig2's sweeps reach the same cells)
 SHAPES = [[6, 2, 2, 2], [6, 5, 4, 2], [6, 16, 16, 3], [6, 17, 33, 4], [6, 64, 2, 2], [6, 2, 64, 3], [6, 63, 64, 4],
-          [6, 64, 64, 3], [6, 32, 17, 2], [6, 20, 32, 4]]
+          [6, 64, 64, 3], [6, 32, 17, 2], [6, 20, 32, 4], [6, 16, 16, 4], [6, 32, 32, 3]]
 
 
 def lanes(H1, H2):

@@ -11,8 +11,9 @@ and genome i = tracker + sigma_i N(0, 1) over all genes, sigma cycling through
 0.3, 1, 3.  Every test asserts on its *reference* run that >= 5 % of the games
 timed out, >= 50 % ended by score and >= 1 % timed out after a point, so a
 population that stops exercising the advance fails loudly; the seeds were picked
-so that the CPU oracle (for ReLU: the same C code with max(0, z) as the
-activation) meets the three conditions at every shape and limit used here.
+so that the CPU oracle (for ReLU: oracle.eval_population(..., activation="relu"))
+meets the three conditions at every shape and limit used here, and every ReLU
+population's general-kernel result is compared with that oracle's (runs()).
 At (timeout_thresh 32, win_score 1) every game times out at frame 34, just
 after the first serve; that is asserted there in place of the three conditions.
 """
@@ -108,6 +109,20 @@ def _serves(res, limits):
     return int(s.sum() + (s < win).all(axis=1).sum())
 
 
+def _assert_general_equals_oracle(ev, general, host, dtype, limits):
+    """The general kernel's ReLU games are the CPU oracle's (activation="relu";
+    pinned to the reference by tests/test_oracle_relu.py), f32 genes as rounded."""
+    import oracle
+    oracle.build()
+    genomes, members, kinds, opp, mult = host
+    if dtype == torch.float32:
+        genomes, members = (a.astype(np.float32).astype(np.float64) for a in (genomes, members))
+    ref = oracle.eval_population(genomes, ev.nodes, kinds, opp, mult, opponents=members, base_seed=ev.seed, n_threads=8,
+                                 timeout_thresh=limits[0], win_score=limits[1], activation="relu")
+    for name in FIELDS:
+        np.testing.assert_array_equal(getattr(general, name).cpu().numpy(), ref[name], err_msg=name)
+
+
 _runs = {}
 
 
@@ -126,6 +141,8 @@ def runs(gpu, family, shape, dtype=torch.float64, limits=DEFAULT, n=N, hall=HALL
                for k in (family + "+advance", family, "general")}
         torch.cuda.synchronize()
         _check_population(got["general"], limits, f"{family} {shape} {dtype} {limits} n={n}")
+        if act == "relu":
+            _assert_general_equals_oracle(ev, got["general"], data["host"], dtype, limits)
         _runs[key] = (ev, data, got)
     return _runs[key]
 

@@ -1,0 +1,152 @@
+"""The ReLU kernels' whole games against the CPU oracle (run with -m gpu): whole
+evaluate() calls at the default limits TIMEOUT_THRESH 2000 / WIN_SCORE 3 against
+oracle.eval_population(..., activation="relu"), which tests/test_oracle_relu.py
+pins to the reference's numbers and to its per-frame numpy loop.  Scores,
+frames, total_frames, rewards, fitness and status are compared with
+np.testing.assert_array_equal: no tolerance anywhere.
+
+The populations are test_gpu_advance's noisy trackers (24 genomes, a hall of 6,
+rows below 12 playing kinds [0,1,2,3,3,3] and the rest all-NN, multipliers of
+both signs), so that 2 000-frame timeouts, periodic rallies and scored games
+occur side by side -- random N(0, 1) ReLU networks mostly decide one index for
+ever and lose 0 : 3 in 180 frames.  [6,1,2], which has no room for a tracker,
+plays N(0, 1) genes.  k_relu and k_relu2 (and their modifier instances) meet the
+oracle in tests/test_gpu_modifier_instances.py.
+"""
+import numpy as np
+import pytest
+import torch
+
+from test_gpu_advance import DEFAULT, _ids, outcome_shares, population
+from test_gpu_parity import _dev_genomes, _gene_count
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("scores", "frames", "total_frames", "rewards", "fitness", "status")
+N, HALL = 24, 6
+
+
+def _f32(a):
+    return np.asarray(a).astype(np.float32).astype(np.float64)
+
+
+def _without_bias(shape, genes):
+    """The genes [n, G] of a biased network with every bias column dropped."""
+    out, off = [], 0
+    for i in range(len(shape) - 1):
+        n = (shape[i] + 1) * shape[i + 1]
+        out.append(genes[:, off:off + n].reshape(len(genes), shape[i + 1], shape[i] + 1)[:, :, :-1].reshape(len(genes), -1))
+        off += n
+    return np.ascontiguousarray(np.concatenate(out, axis=1))
+
+
+def _population(shape, bias=True, n=N, hall=HALL):
+    if min(shape[1:]) < 2:  # no room for the tracker's two units
+        rng = np.random.default_rng(sum(shape))
+        _, _, kinds, opp, mult = population([6, 2, 2], "relu", n=n, hall=hall, seed=sum(shape))
+        return rng.standard_normal((n, _gene_count(shape))), rng.standard_normal((hall, _gene_count(shape))), kinds, opp, mult
+    genomes, members, kinds, opp, mult = population(shape, "relu", n=n, hall=hall, seed=sum(shape))
+    if not bias:
+        genomes, members = _without_bias(shape, genomes), _without_bias(shape, members)
+    return genomes, members, kinds, opp, mult
+
+
+def _play_both(gpu, oracle, shape, kernel, pop, dtype=torch.float64, bias=True, **kw):
+    """(evaluator, EvalResult, trace or None, the oracle's result) of one population."""
+    from pong_amd.device import Evaluator
+    genomes, members, kinds, opp, mult = pop
+    assert (mult < 0).any() and (mult > 0).any() and (kinds[0] == [0, 1, 2, 3, 3, 3]).all() and (kinds[-1] == 3).all()
+    ev = Evaluator(shape, device=gpu, dtype=dtype, bias=bias, activation="relu")
+    assert ev.resolved_kernel(kernel, traced=bool(kw)) == kernel
+    res, trace = ev.evaluate(_dev_genomes(genomes, gpu, dtype), *[torch.tensor(a, device=gpu) for a in (kinds, opp, mult)],
+                             opponents=_dev_genomes(members, gpu, dtype), kernel=kernel, **kw)
+    torch.cuda.synchronize()
+    ref = oracle.eval_population(genomes, shape, kinds, opp, mult, opponents=members, bias=bias, base_seed=ev.seed,
+                                 n_threads=8, activation="relu")
+    return ev, res, trace, ref
+
+
+def _assert_equals_oracle(res, ref, what):
+    for name in FIELDS:
+        np.testing.assert_array_equal(getattr(res, name).cpu().numpy(), ref[name], err_msg=f"{what} {name}")
+    shares = outcome_shares(ref["scores"], DEFAULT)
+    print(f"{what}: {int(ref['frames'].sum())} frames, timed out {shares[0]:.3f}, by score {shares[1]:.3f}, "
+          f"timed out after a point {shares[2]:.3f}")
+    return shares
+
+
+# ------------------------------------------------------ 1 the general kernel ----
+GENERAL = [([6, 64, 3], torch.float64, True), ([6, 200, 4], torch.float32, True), ([6, 33, 64, 4], torch.float64, True),
+           ([6, 130, 100, 2], torch.float64, True), ([6, 1, 2], torch.float64, True), ([6, 16, 3], torch.float64, False)]
+
+
+@pytest.mark.parametrize("shape,dtype,bias", GENERAL, ids=_ids)
+def test_general_kernel_equals_oracle(gpu, oracle, shape, dtype, bias):
+    """np.dot's summation order changes with the width (or_blas_dot's kinds and
+    tails): 1 to 200 units, one and two hidden layers, f32 genes (the rounded
+    values on both sides), a network without bias.  Wherever there is room for the
+    tracker, games time out and games end by score."""
+    genomes, members, kinds, opp, mult = _population(shape, bias)
+    if dtype == torch.float32:
+        genomes, members = _f32(genomes), _f32(members)
+    _, res, _, ref = _play_both(gpu, oracle, shape, "general", (genomes, members, kinds, opp, mult), dtype, bias)
+    shares = _assert_equals_oracle(res, ref, f"general {shape} {dtype} bias {bias}")
+    if min(shape[1:]) >= 2:
+        assert shares[0] > 0 and shares[1] > 0, shares
+
+
+def test_general_kernel_equals_oracle_on_always_f64_genomes(gpu, oracle):
+    """test_gpu_relu2._f64_rows: exact ties, a 1e30 weight, the all-zero genome and
+    a NaN gene (np.maximum keeps the NaN, np.argmax returns the first), as
+    genomes and as hall members."""
+    from test_gpu_relu2 import _f64_rows
+    shape = [6, 33, 64, 4]
+    _, _, kinds, opp, mult = _population(shape)
+    rng = np.random.default_rng(7)
+    genomes, members = _f64_rows(shape, rng, N), _f64_rows(shape, rng, HALL)
+    assert np.isnan(genomes).any() and np.isnan(members).any() and (np.abs(genomes) > 1e29).any()
+    _, res, _, ref = _play_both(gpu, oracle, shape, "general", (genomes, members, kinds, opp, mult))
+    _assert_equals_oracle(res, ref, f"general {shape} always-f64 genomes")
+
+
+def test_general_kernel_traces_equal_oracle(gpu, oracle):
+    """Both paddles' action codes and the ball's visibility of every frame of the
+    first 12 games (two genomes' [0,1,2,3,3,3]) against oracle.play_game's trace."""
+    shape = [6, 33, 64, 4]
+    pop = _population(shape)
+    genomes, members, kinds, opp, mult = pop
+    games, cap = 12, 1 << 14
+    ev, res, trace, ref = _play_both(gpu, oracle, shape, "general", pop, trace_games=games, trace_cap=cap)
+    _assert_equals_oracle(res, ref, f"general {shape} traced")
+    trace = trace.cpu().numpy()
+    assert ref["frames"].ravel()[:games].max() <= cap
+    visible = 0
+    for w in range(games):
+        i, g = divmod(w, 6)
+        k = int(kinds[i, g])
+        r = oracle.play_game(genomes[i], shape, k, members[opp[i, g]] if k == 3 else None, mult[i, g],
+                             oracle.game_seed(ev.seed, g), trace_cap=cap, activation="relu")
+        assert r["frames"] == ref["frames"][i, g] and r["reward"] == ref["rewards"][i, g]
+        np.testing.assert_array_equal(trace[w, :r["frames"]], r["trace"], err_msg=f"game {w}")
+        assert not trace[w, r["frames"]:].any()
+        visible += int(((r["trace"] >> 4) & 1).sum())
+    assert visible > 0
+
+
+# ------------------------------------------------------- 2 the hot kernels ----
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=_ids)
+def test_relu2_block_equals_oracle(gpu, oracle, dtype):
+    shape = [6, 100, 72, 3]  # above 64 units in each hidden layer
+    genomes, members, kinds, opp, mult = _population(shape)
+    if dtype == torch.float32:
+        genomes, members = _f32(genomes), _f32(members)
+    _, res, _, ref = _play_both(gpu, oracle, shape, "relu2_block", (genomes, members, kinds, opp, mult), dtype)
+    shares = _assert_equals_oracle(res, ref, f"relu2_block {shape} {dtype}")
+    assert shares[0] > 0 and shares[1] > 0, shares
+
+
+@pytest.mark.parametrize("shape,n,hall", [([6, 130, 100, 2], N, HALL), ([6, 512, 512, 3], 3, 2)], ids=_ids)
+def test_relu_wide_equals_oracle(gpu, oracle, shape, n, hall):
+    genomes, members, kinds, opp, mult = _population(shape, n=n, hall=hall)
+    _, res, _, ref = _play_both(gpu, oracle, shape, "relu_wide", (genomes, members, kinds, opp, mult))
+    _assert_equals_oracle(res, ref, f"relu_wide {shape}")
