@@ -11,7 +11,8 @@
 //   pg_general.hip       the f64 path: k_general, pg_forward with k_forward_general
 //   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
 //   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
-//   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate with a block per game (widths up to 128)
+//   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate (pg_relu2_bound.h, its block layout) with a block per
+//                        game (widths up to 128)
 //   pg_decide.hip        k_decide (pg_decide)
 //   pg_ga.hip            selection, variation, schedule, row gather and hash
 //   pg_gen.hip, pg_hof.hip, pg_pixels.hip    the generation's device steps, the

@@ -4,7 +4,8 @@
 // (activation_function = ReLU, numpy_nn.py:6-9, 26) or the sigmoid
 // (numpy_nn.py:22-26) in both hidden layers, its decision and its f64
 // re-decision in numpy's order; and the two families' shared host side.  The
-// bounds' arithmetic and their derivations are in pg_relu2_bound.h and
+// bounds' arithmetic and their derivations are in pg_relu2_bound.h (under its
+// lane layout here; k_relu2_block, pg_relu2_block.hip, is its block layout) and
 // pg_sig2_bound.h (they also compile for the host).
 //
 // Lane hl of a half-group holds layer-1 units hl U1 .. hl U1 + U1 - 1 (7
@@ -121,7 +122,7 @@ struct Relu2Bound {
   }
   template <int O>
   static __device__ __forceinline__ float finish(const Sums &s, double asum, const double *c) {
-    return pg_relu2_bound_finish(&s, asum, c, O);
+    return pg_relu2_bound_finish(pg_relu2_layout_lanes(), &s, asum, c, O);
   }
   template <class Net>
   static __device__ __forceinline__ void set(Net &n, float e) {

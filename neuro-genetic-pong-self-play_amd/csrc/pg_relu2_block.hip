@@ -26,8 +26,8 @@
 // networks' z^_o = (wave 0's sum + wave 1's sum) + b3_o -- in that order --
 // from LDS, and takes both decisions itself under the networks' bounds, also
 // in LDS: all 256 threads hold the same two action codes with no further
-// exchange.  That is the order pg_relu2_block_bound.h's chain lengths bound and
-// tests/_relu2_block_model.py restates.
+// exchange.  That is the order pg_relu2_bound.h's block chain lengths bound and
+// tests/_relu2_model.py restates.
 //
 // The decision is k_relu2's (relu_certify, pg_relu.hpp): index 0 if t1 <= -e,
 // the index of t1 if t1 > e and t1 - t2 > 2e, else the f64 forward from the
@@ -50,7 +50,7 @@
 #include "pg_device.hpp"
 #include "pg_eval.hpp"
 #include "pg_relu.hpp"
-#include "pg_relu2_block_bound.h"
+#include "pg_relu2_bound.h"
 
 namespace pg {
 
@@ -75,7 +75,7 @@ struct alignas(16) BlockLds {
   float h[2][kBlockH];            // the f32 all-gather rows
   float part[4][4];               // [wave][o]: the wave's sum of the O products
   float c[2][4];                  // [n][o]: output biases
-  float e[2];                     // [n]: |z^_o - z64_o| <= e (pg_relu2_block_bound.h); inf: always f64
+  float e[2];                     // [n]: |z^_o - z64_o| <= e (pg_relu2_bound.h); inf: always f64
   int game;                       // the game thread 0 took
   double d[2][2 * kBlockH + 4];   // [n]: the f64 path's activations (layer 1, layer 2, outputs); the load's A_j
   double red[4][3 * PG_RELU_MAX_OUT + 3];  // [wave]: the load's sums of the bound
@@ -178,7 +178,7 @@ __device__ __forceinline__ void block_load(BlockNet<O> &n, const WT *__restrict_
       }
       t.B = r0[3 * O] + r1[3 * O];
       t.W2 = r0[3 * O + 1] + r1[3 * O + 1];
-      e = pg_relu2_block_bound_finish(&t, r0[3 * O + 2] + r1[3 * O + 2], c, O);
+      e = pg_relu2_bound_finish(pg_relu2_layout_block(), &t, r0[3 * O + 2] + r1[3 * O + 2], c, O);
     }
     lds.e[net] = e;
 #pragma unroll

@@ -17,18 +17,15 @@ population's general-kernel result is compared with that oracle's (runs()).
 At (timeout_thresh 32, win_score 1) every game times out at frame 34, just
 after the first serve; that is asserted there in place of the three conditions.
 """
-import importlib
-import random
 
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _dev_genomes
+from _gpu_support import FIELDS, dev_genomes, dropin_config, dropin_fitness, ids, same
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 SIGMAS = (0.3, 1.0, 3.0)
 N, HALL = 192, 24
 FAMILIES = {"relu": "relu", "relu2": "relu", "sig2": "sigmoid"}  # kernel name -> activation
@@ -42,10 +39,6 @@ DEFAULT, SHORT, SERVE = (0, 0), (600, 2), (32, 1)  # (timeout_thresh, win_score)
 # the CPU: the wider ReLU trackers time out in 4.6-6 % of their games under most seeds, in 6-10 % under these
 SEEDS = {((6, 65, 3), "relu", N): 128, ((6, 129, 4), "relu", N): 114, ((6, 17, 3, 3), "relu", N): 57,
          ((6, 33, 64, 4), "relu", N): 50}
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, (list, tuple)) else str(v).replace("torch.", "")
 
 
 def _genes(shape):
@@ -135,7 +128,7 @@ def runs(gpu, family, shape, dtype=torch.float64, limits=DEFAULT, n=N, hall=HALL
         act = FAMILIES[family]
         genomes, members, kinds, opp, mult = population(shape, act, n, hall)
         ev = Evaluator(shape, device=gpu, dtype=dtype, activation=act, timeout_thresh=limits[0], win_score=limits[1])
-        data = dict(genomes=_dev_genomes(genomes, gpu, dtype), opponents=_dev_genomes(members, gpu, dtype),
+        data = dict(genomes=dev_genomes(genomes, gpu, dtype), opponents=dev_genomes(members, gpu, dtype),
                     sched=[torch.tensor(a, device=gpu) for a in (kinds, opp, mult)], host=(genomes, members, kinds, opp, mult))
         got = {k: ev.evaluate(data["genomes"], *data["sched"], opponents=data["opponents"], kernel=k)[0]
                for k in (family + "+advance", family, "general")}
@@ -147,14 +140,9 @@ def runs(gpu, family, shape, dtype=torch.float64, limits=DEFAULT, n=N, hall=HALL
     return _runs[key]
 
 
-def _same(a, b, what=""):
-    for name in FIELDS:
-        assert torch.equal(getattr(a, name), getattr(b, name)), (name, what)
-
-
 def _assert_advance_equals_stepping(family, adv, base, ref, limits, what):
-    _same(adv, base, what)
-    _same(adv, ref, what)
+    same(adv, base, what=what)
+    same(adv, ref, what=what)
     ca, cb = adv.counters.cpu().numpy(), base.counters.cpu().numpy()
     frames = int(ref.frames.sum())
     print(f"{what}: frames {frames}, stepped {ca[0]}, rally [8] {ca[8]} ({ca[8] / frames:.3f}), serve delays [12] "
@@ -178,11 +166,11 @@ def test_serve_delay_formula_on_the_split_kernel(gpu):
     shape = [6, 2, 2]
     genomes, members, kinds, opp, mult = population(shape, "sigmoid")
     ev = Evaluator(shape, device=gpu)
-    args = [_dev_genomes(genomes, gpu)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
-    got = {k: ev.evaluate(*args, opponents=_dev_genomes(members, gpu), kernel=k)[0] for k in ("split", "general")}
+    args = [dev_genomes(genomes, gpu)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
+    got = {k: ev.evaluate(*args, opponents=dev_genomes(members, gpu), kernel=k)[0] for k in ("split", "general")}
     torch.cuda.synchronize()
     _check_population(got["general"], DEFAULT, f"split {shape}")
-    _same(got["split"], got["general"])
+    same(got["split"], got["general"])
     c = got["split"].counters.cpu().numpy()
     assert c[12] == 29 * _serves(got["general"], DEFAULT) and c[8] > 0
     assert c[0] + c[8] + c[12] == int(got["general"].frames.sum())
@@ -192,7 +180,7 @@ def test_serve_delay_formula_on_the_split_kernel(gpu):
 CASES = [(f, s, torch.float64) for f in FAMILIES for s in SHAPES[f]] + [(f, F32_SHAPE[f], torch.float32) for f in FAMILIES]
 
 
-@pytest.mark.parametrize("family,shape,dtype", CASES, ids=_ids)
+@pytest.mark.parametrize("family,shape,dtype", CASES, ids=ids)
 def test_advance_equals_stepping(gpu, family, shape, dtype):
     """"X+advance" against "X" and "general" at default limits: every output
     array equal; [0] + [8] + [12] = the episodes' frames = the stepping kernel's
@@ -213,7 +201,7 @@ def test_sig2_advance_matches_oracle(gpu, oracle):
 
 
 # --------------------------------------------------------------- 2 limits ----
-@pytest.mark.parametrize("limits", [SHORT, SERVE], ids=_ids)
+@pytest.mark.parametrize("limits", [SHORT, SERVE], ids=ids)
 @pytest.mark.parametrize("family", list(FAMILIES))
 def test_advance_under_other_limits(gpu, family, limits):
     """TIMEOUT_THRESH 600 / WIN_SCORE 2, and 32 / 1, where the timeout passes
@@ -233,7 +221,7 @@ def test_traced_launch_runs_with_the_advance_off(gpu, family):
                           trace_cap=2048) for k in (family + "+advance", "general")}
     torch.cuda.synchronize()
     (adv, adv_tr), (ref, ref_tr) = out[family + "+advance"], out["general"]
-    _same(adv, ref)
+    same(adv, ref)
     assert torch.equal(adv_tr, ref_tr) and int(adv_tr.any())
     c = adv.counters.cpu().numpy()
     assert c[8] == 0 and c[12] == 0 and c[0] == int(ref.frames.sum())
@@ -241,7 +229,7 @@ def test_traced_launch_runs_with_the_advance_off(gpu, family):
 
 
 # -------------------------------------------------------------- 4 reloads ----
-@pytest.mark.parametrize("family,shape,n", [("relu2", [6, 2, 2, 2], 4096), ("sig2", [6, 33, 64, 4], 1024)], ids=_ids)
+@pytest.mark.parametrize("family,shape,n", [("relu2", [6, 2, 2, 2], 4096), ("sig2", [6, 33, 64, 4], 1024)], ids=ids)
 def test_groups_reload_games_with_a_fresh_search(gpu, family, shape, n):
     """More games than the launch has lane groups, so every group takes further
     games from the queue: a rally search left open by a group's previous game
@@ -255,17 +243,17 @@ def test_groups_reload_games_with_a_fresh_search(gpu, family, shape, n):
 
 
 # ----------------------------------------------------------------- 5 AUTO ----
-@pytest.mark.parametrize("family,shape", [("relu", [6, 2, 2]), ("relu2", [6, 2, 2, 2])], ids=_ids)
+@pytest.mark.parametrize("family,shape", [("relu", [6, 2, 2]), ("relu2", [6, 2, 2, 2])], ids=ids)
 def test_auto_advance_in_the_relu_scopes(gpu, family, shape):
     ev, data, got = runs(gpu, family, shape)
     auto, _ = ev.evaluate(data["genomes"], *data["sched"], opponents=data["opponents"], kernel="auto+advance")
     torch.cuda.synchronize()
-    _same(auto, got[family + "+advance"])
+    same(auto, got[family + "+advance"])
     assert torch.equal(auto.counters, got[family + "+advance"].counters) and int(auto.counters[12]) > 0
 
 
 @pytest.mark.parametrize("activation,shape,general", [("sigmoid", [6, 64, 3], False), ("relu", [6, 4, 4, 4, 2], True),
-                                                      ("sigmoid", [6, 16, 16, 3], True)], ids=_ids)
+                                                      ("sigmoid", [6, 16, 16, 3], True)], ids=ids)
 def test_auto_advance_changes_nothing_elsewhere(gpu, activation, shape, general):
     """Where AUTO resolves to SPLIT ([6,64,3] sigmoid) or GENERAL (a ReLU net
     outside k_relu's and k_relu2's scopes; a two-hidden-layer sigmoid net, which
@@ -273,12 +261,12 @@ def test_auto_advance_changes_nothing_elsewhere(gpu, activation, shape, general)
     from pong_amd.device import Evaluator
     genomes, members, kinds, opp, mult = population(shape, activation, n=48, hall=8)
     ev = Evaluator(shape, device=gpu, activation=activation)
-    args = [_dev_genomes(genomes, gpu)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
-    got = {k: ev.evaluate(*args, opponents=_dev_genomes(members, gpu), kernel=k)[0]
+    args = [dev_genomes(genomes, gpu)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
+    got = {k: ev.evaluate(*args, opponents=dev_genomes(members, gpu), kernel=k)[0]
            for k in ("auto+advance", "auto", "general")}
     torch.cuda.synchronize()
-    _same(got["auto+advance"], got["auto"])
-    _same(got["auto+advance"], got["general"])
+    same(got["auto+advance"], got["auto"])
+    same(got["auto+advance"], got["general"])
     assert torch.equal(got["auto+advance"].counters, got["auto"].counters)
     c, cg = got["auto+advance"].counters.cpu().numpy(), got["general"].counters.cpu().numpy()
     if general:
@@ -306,43 +294,18 @@ def test_device_ga_auto_advance_generations(gpu):
     assert int(ga.last.counters[12]) > 0 and int(ga_b.last.counters[12]) == 0  # k_relu_adv played
 
 
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.fixture
 def relu_advance_dropin():
     """config.ACTIVATION = "relu" and config.KERNEL = "auto+advance" as a user sets them."""
-    import config
-    import numpy_nn
-    saved = (config.ACTIVATION, config.KERNEL)
-    config.ACTIVATION, config.KERNEL = "relu", "auto+advance"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="relu", kernel="auto+advance"):
+        import config
         yield config
-    finally:
-        config.ACTIVATION, config.KERNEL = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_equals_auto(gpu, relu_advance_dropin):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on a [6,16,3] ReLU network with
     config.KERNEL = "auto+advance" against the same call with "auto": the same
     hall, the same random seed, the same fitness."""
-    import ga
     import main
     import utils
     config = relu_advance_dropin
@@ -355,18 +318,13 @@ def test_dropin_evaluate_equals_auto(gpu, relu_advance_dropin):
         hall = rng.standard_normal((4, G))
         inds = [list(g) for g in rng.standard_normal((24, G))]
 
-        def fitness():  # (pick_hall_of_famer shuffles the hall in place: a fresh one, in the same order, per run)
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
-
         ev = main._evaluator()
         assert ev.activation == "relu" and list(ev.nodes) == shape and ev.kernel == "auto+advance"
-        got = fitness()
+        got = dropin_fitness(hall, inds)
         config.KERNEL = "auto"
         ev_b = main._evaluator()
         assert ev_b is not ev and ev_b.kernel == "auto"
-        want = fitness()
+        want = dropin_fitness(hall, inds)
         assert got == want and len(set(got)) >= 3
     finally:
         utils.NETWORK_SHAPE, main.hall_of_fame = saved

@@ -6,24 +6,9 @@ import random
 import numpy as np
 import pytest
 
+from _gpu_support import HoF, Member
+
 pytestmark = pytest.mark.gpu
-
-
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
 
 
 def test_toolbox_map_evaluate_matches_reference(gpu, golden):
@@ -36,7 +21,7 @@ def test_toolbox_map_evaluate_matches_reference(gpu, golden):
     try:
         for case in golden("evaluate.json") + golden("evaluate_s3.json"):
             utils.NETWORK_SHAPE = case["shape"]
-            main.hall_of_fame = _HoF([_Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])])
+            main.hall_of_fame = HoF([Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])])
             random.seed(case["random_seed"])
             inds = [list(g) for g in case["individuals"]]
             got = [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _assert_same, _dev_genomes, _gene_count, _schedule
+from _gpu_support import assert_same, dev_genomes, gene_count, schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -23,9 +23,9 @@ LIMITS = [(59, 0), (119, 0), (0, 1), (0, 2), (59, 5), (2000, 3)]
 
 def _run(ev, oracle, gpu, genomes, opponents, kinds, opp, mult, thresh, win, horizon=0):
     dt = ev.dtype
-    res, _ = ev.evaluate(_dev_genomes(genomes, gpu, dt), torch.tensor(kinds, device=gpu),
+    res, _ = ev.evaluate(dev_genomes(genomes, gpu, dt), torch.tensor(kinds, device=gpu),
                          torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                         opponents=_dev_genomes(opponents, gpu, dt))
+                         opponents=dev_genomes(opponents, gpu, dt))
     torch.cuda.synchronize()
     ref = oracle.eval_population(genomes, ev.nodes, kinds, opp, mult, opponents=opponents, bias=ev.bias,
                                  base_seed=ev.seed, n_threads=8, horizon=horizon, timeout_thresh=thresh,
@@ -39,16 +39,16 @@ def test_limits_match_oracle(gpu, oracle, kernel, lanes, thresh, win):
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
     rng = np.random.default_rng(thresh * 10 + win)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 256 if kernel == "split" else 64, 32
     genomes = rng.standard_normal((n, G)) * 3.0
     opponents = rng.standard_normal((H, G)) * 3.0
-    kinds, opp, mult = _schedule(rng, n, 6, H)
+    kinds, opp, mult = schedule(rng, n, 6, H)
     kinds[: n // 2] = 3  # half the population in all-network games
     ev = Evaluator(shape, device=gpu, kernel=kernel, group_lanes=lanes,
                    precision="f64" if kernel == "general" else "certified", timeout_thresh=thresh, win_score=win)
     res, ref = _run(ev, oracle, gpu, genomes, opponents, kinds, opp, mult, thresh, win)
-    _assert_same(res, ref)
+    assert_same(res, ref)
     if win:
         assert int(res.scores.max()) <= win
 
@@ -62,15 +62,15 @@ def test_limits_horizon_matches_oracle(gpu, oracle, thresh, win):
     shape = [6, 64, 3]
     T = 1000
     rng = np.random.default_rng(thresh + 7 * win)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 128, 32
     genomes = rng.standard_normal((n, G)) * 3.0
     opponents = rng.standard_normal((H, G)) * 3.0
-    kinds, opp, mult = _schedule(rng, n, 6, H)
+    kinds, opp, mult = schedule(rng, n, 6, H)
     kinds[: n // 2] = 3
     ev = Evaluator(shape, device=gpu, horizon=T, timeout_thresh=thresh, win_score=win)
     res, ref = _run(ev, oracle, gpu, genomes, opponents, kinds, opp, mult, thresh, win, horizon=T)
-    _assert_same(res, ref)
+    assert_same(res, ref)
     assert (res.frames.cpu().numpy() == T).all()
 
 
@@ -79,21 +79,21 @@ def test_limits_wide_matches_oracle(gpu, oracle, thresh, win):
     from pong_amd.device import Evaluator
     shape = [6, 64, 64, 3]
     rng = np.random.default_rng(thresh + win + 1)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 24, 6
     genomes = rng.standard_normal((n, G)) * 2.0
     opponents = rng.standard_normal((H, G)) * 2.0
-    kinds, opp, mult = _schedule(rng, n, 6, H)
+    kinds, opp, mult = schedule(rng, n, 6, H)
     ev = Evaluator(shape, device=gpu, kernel="wide", timeout_thresh=thresh, win_score=win)
     res, ref = _run(ev, oracle, gpu, genomes, opponents, kinds, opp, mult, thresh, win)
-    _assert_same(res, ref)
+    assert_same(res, ref)
 
 
 def test_limits_refused_out_of_range(gpu):
     from pong_amd import _lib
     from pong_amd.device import Evaluator
     shape = [6, 8, 3]
-    G = _gene_count(shape)
+    G = gene_count(shape)
     z = torch.zeros((2, 6), dtype=torch.int32, device=gpu)
     for thresh, win in ((31, 0), (1 << 21, 0), (0, -1)):
         ev = Evaluator(shape, device=gpu, timeout_thresh=thresh, win_score=win)

@@ -22,9 +22,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_advance import (DEFAULT, FAMILIES, FIELDS, _assert_advance_equals_stepping, _ids, outcome_shares,
-                              population)
-from test_gpu_parity import _dev_genomes
+from _gpu_support import FIELDS, dev_genomes
+from test_gpu_advance import DEFAULT, FAMILIES, _assert_advance_equals_stepping, outcome_shares, population
 from test_gpu_solo import NN, _equal
 
 N_CELL, HALL_CELL = 96, 24
@@ -151,8 +150,8 @@ def test_modifier_instances_equal_the_oracle(gpu, oracle, cell):
     kernels = (family, family + "+advance", family + "+solo", family + "+advance+solo", "general")
     for k in kernels:  # the instance asked for is the one that runs: no fallback to the base kernel
         assert ev.resolved_kernel(k) == k, (k, ev.resolved_kernel(k))
-    args = [_dev_genomes(genomes, gpu, dtype)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
-    hall = _dev_genomes(members, gpu, dtype)
+    args = [dev_genomes(genomes, gpu, dtype)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
+    hall = dev_genomes(members, gpu, dtype)
     got = {k: ev.evaluate(*args, opponents=hall, kernel=k)[0] for k in kernels}
     torch.cuda.synchronize()
     ref = oracle_result(oracle, cell, pop, base_seed=ev.seed)

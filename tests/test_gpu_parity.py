@@ -7,18 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from _gpu_support import assert_same, dev_genomes, gene_count, run_both, schedule
+
 pytestmark = pytest.mark.gpu
 
 SHAPES_RES = [[6, 2, 2], [6, 64, 3], [6, 64, 2], [6, 16, 3], [6, 100, 3]]
-
-
-def _dev_genomes(a, dev, dtype=torch.float64):
-    return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=dev)
-
-
-def _gene_count(shape, bias=True):
-    b = 1 if bias else 0
-    return sum((shape[i] + b) * shape[i + 1] for i in range(len(shape) - 1))
 
 
 # ------------------------------------------------------------------ forward
@@ -31,7 +24,7 @@ def test_forward_matches_reference_golden(gpu, golden, key, precision):
     bias = bool(g[f"{key}__bias"])
     genes, gidx, x = g[f"{key}__genes"], g[f"{key}__gidx"], g[f"{key}__x"]
     ev = Evaluator(shape, bias=bias, device=gpu, precision=precision)
-    idx, act = ev.forward(_dev_genomes(genes, gpu), torch.tensor(x, dtype=torch.float64, device=gpu),
+    idx, act = ev.forward(dev_genomes(genes, gpu), torch.tensor(x, dtype=torch.float64, device=gpu),
                           genome_index=torch.tensor(gidx, dtype=torch.int32, device=gpu))
     np.testing.assert_array_equal(idx.cpu().numpy(), g[f"{key}__idx"])
     tol = 1e-5 if (precision == "certified" and len(shape) == 3) else 1e-12
@@ -48,10 +41,10 @@ def test_forward_wide_golden(gpu, golden, name):
     shape = [6, 512, 512, 3]
     ev = Evaluator(shape, device=gpu, precision="f64")
     for c in cases:
-        genes = np.random.default_rng(c["seed"]).standard_normal(_gene_count(shape)) * c["sigma"]
+        genes = np.random.default_rng(c["seed"]).standard_normal(gene_count(shape)) * c["sigma"]
         genes = genes.astype(np.float32).astype(np.float64)
         assert hashlib.sha256(genes.tobytes()).hexdigest() == c["genes_sha256"]
-        idx, act = ev.forward(_dev_genomes(genes[None], gpu), torch.tensor([c["x"]], dtype=torch.float64, device=gpu))
+        idx, act = ev.forward(dev_genomes(genes[None], gpu), torch.tensor([c["x"]], dtype=torch.float64, device=gpu))
         assert int(idx[0]) == c["idx"]
         np.testing.assert_allclose(act[0].cpu().numpy(), c["act"], rtol=0, atol=1e-12)
 
@@ -61,7 +54,7 @@ def test_forward_certified_equals_f64(gpu, oracle, shape):
     """The certified f32 argmax equals the f64 argmax on every decision (1.5M+ passes)."""
     from pong_amd.device import Evaluator
     rng = np.random.default_rng(len(shape) * 100 + shape[1])
-    G = _gene_count(shape)
+    G = gene_count(shape)
     ev = Evaluator(shape, device=gpu)
     n_gen, per = 2048, 192
     tot_slow = 0
@@ -70,7 +63,7 @@ def test_forward_certified_equals_f64(gpu, oracle, shape):
             genes = rng.random((n_gen, G))
         else:
             genes = rng.standard_normal((n_gen, G)) * dist
-        dg = _dev_genomes(genes, gpu)
+        dg = dev_genomes(genes, gpu)
         gi = torch.tensor(np.repeat(np.arange(n_gen), per), dtype=torch.int32, device=gpu)
         k = rng.integers(0, 321, size=(n_gen * per, 6))
         x = torch.tensor(k / 320.0, dtype=torch.float64, device=gpu)
@@ -115,60 +108,27 @@ def test_physics_matches_oracle(gpu, oracle):
 
 
 # --------------------------------------------------------------- episodes
-def _schedule(rng, n, n_games, n_opp):
-    kinds = np.zeros((n, n_games), np.int32)
-    for g in range(n_games):
-        kinds[:, g] = [0, 1, 2, 3, 3, 3][g % 6]
-    flip = rng.random((n, n_games)) < 0.15
-    kinds[flip] = 0  # empty-HoF style games
-    opp = rng.integers(0, n_opp, size=(n, n_games)).astype(np.int32)
-    mult = np.ones((n, n_games))
-    hof_games = kinds == 3
-    mult[hof_games] = np.round(rng.normal(size=hof_games.sum()), 3)
-    return kinds, opp, mult
-
-
-def _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu, **kw):
-    dt = ev.dtype
-    res, _ = ev.evaluate(_dev_genomes(genomes, gpu, dt), torch.tensor(kinds, device=gpu),
-                         torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                         opponents=_dev_genomes(opponents, gpu, dt), **kw)
-    torch.cuda.synchronize()
-    ref = oracle.eval_population(genomes, ev.nodes, kinds, opp, mult, opponents=opponents, bias=ev.bias,
-                                 base_seed=ev.seed, n_threads=8)
-    return res, ref
-
-
-def _assert_same(res, ref):
-    np.testing.assert_array_equal(res.scores.cpu().numpy(), ref["scores"])
-    np.testing.assert_array_equal(res.frames.cpu().numpy(), ref["frames"])
-    np.testing.assert_array_equal(res.total_frames.cpu().numpy(), ref["total_frames"])
-    np.testing.assert_array_equal(res.rewards.cpu().numpy(), ref["rewards"])
-    np.testing.assert_array_equal(res.fitness.cpu().numpy(), ref["fitness"])
-    np.testing.assert_array_equal(res.status.cpu().numpy(), ref["status"])
-
-
 @pytest.mark.parametrize("shape", SHAPES_RES + [[6, 8, 8, 3]])
 @pytest.mark.parametrize("dist", ["init", "n3"])
 def test_eval_matches_oracle(gpu, oracle, shape, dist):
     from pong_amd.device import Evaluator
     rng = np.random.default_rng(sum(shape) + (0 if dist == "init" else 7))
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 97, 13  # ragged sizes on purpose
     draw = (lambda s: rng.random(s)) if dist == "init" else (lambda s: rng.standard_normal(s) * 3.0)
     genomes, opponents = draw((n, G)), draw((H, G))
-    kinds, opp, mult = _schedule(rng, n, 6, H)
+    kinds, opp, mult = schedule(rng, n, 6, H)
     ev = Evaluator(shape, device=gpu)
-    res, ref = _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
-    _assert_same(res, ref)
+    res, ref = run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
+    assert_same(res, ref)
     # simulated env steps + periodic-rally frames not simulated = the episodes' frames
     assert int(res.counters[0]) + int(res.counters[8]) + int(res.counters[12]) == int(ref["frames"].sum())
     if len(shape) == 3:  # the other kernels must agree too
         for kernel, precision in (("general", "f64"),):
-            res2, _ = ev.evaluate(_dev_genomes(genomes, gpu), torch.tensor(kinds, device=gpu),
+            res2, _ = ev.evaluate(dev_genomes(genomes, gpu), torch.tensor(kinds, device=gpu),
                                   torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                                  opponents=_dev_genomes(opponents, gpu), kernel=kernel, precision=precision)
-            _assert_same(res2, ref)
+                                  opponents=dev_genomes(opponents, gpu), kernel=kernel, precision=precision)
+            assert_same(res2, ref)
 
 
 @pytest.mark.parametrize("kernel,lanes,hidden", [
@@ -180,12 +140,12 @@ def test_eval_kernel_layouts(gpu, oracle, kernel, lanes, hidden):
     from pong_amd.device import Evaluator
     shape = [6, hidden, 3]
     rng = np.random.default_rng(lanes * 1000 + hidden)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     genomes, opponents = rng.standard_normal((64, G)), rng.standard_normal((7, G))
-    kinds, opp, mult = _schedule(rng, 64, 6, 7)
+    kinds, opp, mult = schedule(rng, 64, 6, 7)
     ev = Evaluator(shape, device=gpu, group_lanes=lanes, kernel=kernel)
-    res, ref = _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
-    _assert_same(res, ref)
+    res, ref = run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
+    assert_same(res, ref)
 
 
 def test_eval_near_saturation_matches_oracle(gpu, oracle):
@@ -195,7 +155,7 @@ def test_eval_near_saturation_matches_oracle(gpu, oracle):
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
     rng = np.random.default_rng(5)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 1536, 384
     genomes = rng.standard_normal((n, G)) * 3.0
     opponents = genomes[:H]
@@ -203,8 +163,8 @@ def test_eval_near_saturation_matches_oracle(gpu, oracle):
     opp = ((np.arange(n)[:, None] * 6 + np.arange(6)[None, :]) % H).astype(np.int32)
     mult = np.ones((n, 6))
     ev = Evaluator(shape, device=gpu, kernel="split")
-    res, ref = _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
-    _assert_same(res, ref)
+    res, ref = run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
+    assert_same(res, ref)
     c = res.counters.cpu().numpy()
     assert c[4] > 0 and c[5] > 0 and c[6] > 0, c    # in-wave and service certificates both exercised
     assert c[8] > 0, c                              # and periodic rallies skipped to their timeout
@@ -220,7 +180,7 @@ def test_eval_forward_count_by_frames(gpu, oracle):
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
     rng = np.random.default_rng(17)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 384, 128
     genomes = rng.standard_normal((n, G)) * 3.0
     opponents = rng.standard_normal((H, G)) * 3.0
@@ -230,8 +190,8 @@ def test_eval_forward_count_by_frames(gpu, oracle):
     counters = []
     for lanes in (8, 16):
         ev = Evaluator(shape, device=gpu, group_lanes=lanes, kernel="split")
-        res, ref = _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
-        _assert_same(res, ref)
+        res, ref = run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
+        assert_same(res, ref)
         c = res.counters.cpu().numpy().astype(np.int64)
         points = int(res.scores.sum())
         assert c[1] == 2 * (c[0] - points), (lanes, c[0], c[1], points)
@@ -245,20 +205,20 @@ def test_eval_f32_genomes(gpu, oracle):
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
     rng = np.random.default_rng(11)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     genomes = rng.standard_normal((50, G)).astype(np.float32).astype(np.float64)
     opponents = rng.standard_normal((5, G)).astype(np.float32).astype(np.float64)
-    kinds, opp, mult = _schedule(rng, 50, 6, 5)
+    kinds, opp, mult = schedule(rng, 50, 6, 5)
     ev = Evaluator(shape, device=gpu, dtype=torch.float32)
-    res, ref = _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
-    _assert_same(res, ref)
+    res, ref = run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
+    assert_same(res, ref)
 
 
 def test_eval_edge_cases(gpu, oracle):
     from pong_amd.device import Evaluator
     shape = [6, 2, 2]
     ev = Evaluator(shape, device=gpu)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     # empty population
     res, _ = ev.evaluate(torch.zeros((0, G), dtype=torch.float64, device=gpu),
                          torch.zeros((0, 6), dtype=torch.int32, device=gpu),
@@ -295,7 +255,7 @@ def test_episode_traces_match_reference(gpu, golden, name, kernel):
     for ep in eps:
         shape = ep["shape"]
         ev = Evaluator(shape, device=gpu, n_games=ep["game_index"] + 1, kernel=kernel)
-        G = _gene_count(shape)
+        G = gene_count(shape)
         n_games = ep["game_index"] + 1
         kinds = np.zeros((1, n_games), np.int32)
         kinds[0, ep["game_index"]] = ep["kind"]
@@ -304,9 +264,9 @@ def test_episode_traces_match_reference(gpu, golden, name, kernel):
         mult[0, ep["game_index"]] = ep["mult"]
         opponents = np.array([ep["opp"]]) if ep["opp"] is not None else np.zeros((1, G))
         cap = ep["frames"] + 1
-        res, trace = ev.evaluate(_dev_genomes(np.array([ep["right"]]), gpu), torch.tensor(kinds, device=gpu),
+        res, trace = ev.evaluate(dev_genomes(np.array([ep["right"]]), gpu), torch.tensor(kinds, device=gpu),
                                  torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                                 opponents=_dev_genomes(opponents, gpu), trace_games=n_games, trace_cap=cap)
+                                 opponents=dev_genomes(opponents, gpu), trace_games=n_games, trace_cap=cap)
         gi = ep["game_index"]
         assert int(res.frames[0, gi]) == ep["frames"]
         assert int(res.scores[0, gi, 0]) == ep["score1"] and int(res.scores[0, gi, 1]) == ep["score2"]
@@ -315,9 +275,9 @@ def test_episode_traces_match_reference(gpu, golden, name, kernel):
         # the action env.step received at frame t+1 is the decision traced at frame t
         np.testing.assert_array_equal(tr[:-1] & 3, np.array(ep["right_actions"][1:]))
         np.testing.assert_array_equal((tr[:-1] >> 2) & 3, np.array(ep["left_actions"][1:]))
-        res2, _ = ev.evaluate(_dev_genomes(np.array([ep["right"]]), gpu), torch.tensor(kinds, device=gpu),
+        res2, _ = ev.evaluate(dev_genomes(np.array([ep["right"]]), gpu), torch.tensor(kinds, device=gpu),
                               torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                              opponents=_dev_genomes(opponents, gpu))
+                              opponents=dev_genomes(opponents, gpu))
         assert int(res2.frames[0, gi]) == ep["frames"]
         assert int(res2.scores[0, gi, 0]) == ep["score1"] and int(res2.scores[0, gi, 1]) == ep["score2"]
         assert float(res2.rewards[0, gi]) == ep["reward"]
@@ -330,7 +290,7 @@ def test_full_size_properties(gpu, oracle):
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
     n, H = 65536, 16384
-    G = _gene_count(shape)
+    G = gene_count(shape)
     gen = torch.Generator(device=gpu).manual_seed(1234)
     genomes = torch.randn((n, G), generator=gen, dtype=torch.float64, device=gpu) * 3.0
     opponents = genomes[:H].contiguous()
@@ -369,22 +329,22 @@ def test_horizon_matches_oracle(gpu, oracle, dtype, T):
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
     rng = np.random.default_rng(T + (0 if dtype == torch.float64 else 1))
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 192, 48
     genomes = rng.standard_normal((n, G)) * 3.0
     opponents = rng.standard_normal((H, G)) * 3.0
     if dtype == torch.float32:
         genomes = genomes.astype(np.float32).astype(np.float64)
         opponents = opponents.astype(np.float32).astype(np.float64)
-    kinds, opp, mult = _schedule(rng, n, 6, H)
+    kinds, opp, mult = schedule(rng, n, 6, H)
     kinds[: n // 2] = 3  # half the population in all-network games
     ev = Evaluator(shape, device=gpu, dtype=dtype, horizon=T)
-    res, _ = ev.evaluate(_dev_genomes(genomes, gpu, dtype), torch.tensor(kinds, device=gpu),
+    res, _ = ev.evaluate(dev_genomes(genomes, gpu, dtype), torch.tensor(kinds, device=gpu),
                          torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                         opponents=_dev_genomes(opponents, gpu, dtype))
+                         opponents=dev_genomes(opponents, gpu, dtype))
     torch.cuda.synchronize()
     ref = oracle.eval_population(genomes, shape, kinds, opp, mult, opponents=opponents, n_threads=8, horizon=T)
-    _assert_same(res, ref)
+    assert_same(res, ref)
     c = res.counters.cpu().numpy()
     assert c[0] == n * 6 * T and c[8] == 0 and c[12] == 0, c  # every frame stepped
     assert (res.frames.cpu().numpy() == T).all()
@@ -404,7 +364,7 @@ def test_horizon_long_slots_past_the_serve_table(gpu, oracle, dtype):
     shape = [6, 64, 3]
     T = 9000
     rng = np.random.default_rng(5)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 64, 16
     genomes = rng.standard_normal((n, G)) * 3.0
     opponents = rng.standard_normal((H, G)) * 3.0
@@ -415,14 +375,14 @@ def test_horizon_long_slots_past_the_serve_table(gpu, oracle, dtype):
     opp = rng.integers(0, H, (n, 6)).astype(np.int32)
     mult = np.where(kinds == 3, 0.5, 1.0)
     ev = Evaluator(shape, device=gpu, dtype=dtype, horizon=T)
-    res, _ = ev.evaluate(_dev_genomes(genomes, gpu, dtype), torch.tensor(kinds, device=gpu),
+    res, _ = ev.evaluate(dev_genomes(genomes, gpu, dtype), torch.tensor(kinds, device=gpu),
                          torch.tensor(opp, device=gpu), torch.tensor(mult, device=gpu),
-                         opponents=_dev_genomes(opponents, gpu, dtype))
+                         opponents=dev_genomes(opponents, gpu, dtype))
     torch.cuda.synchronize()
     ref = oracle.eval_population(genomes, shape, kinds, opp, mult, opponents=opponents, n_threads=8, horizon=T)
     points = ref["scores"].sum(-1)
     assert (points > 64).sum() > n, "the regime past the serve table was not exercised"
-    _assert_same(res, ref)
+    assert_same(res, ref)
     assert (res.frames.cpu().numpy() == T).all()
 
 
@@ -430,7 +390,7 @@ def test_horizon_rejected_where_unsupported(gpu):
     from pong_amd import _lib
     from pong_amd.device import Evaluator
     shape = [6, 16, 3]
-    G = _gene_count(shape)
+    G = gene_count(shape)
     ev = Evaluator(shape, device=gpu, horizon=100)
     z = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
     with pytest.raises(_lib.PongGAError):  # only the [6, 33..64, 3] layout has the horizon instance
@@ -438,5 +398,5 @@ def test_horizon_rejected_where_unsupported(gpu):
                     torch.ones((4, 6), dtype=torch.float64, device=gpu))
     ev = Evaluator([6, 64, 3], device=gpu, horizon=100)
     with pytest.raises(_lib.PongGAError):  # and it runs untraced
-        ev.evaluate(torch.zeros((4, _gene_count([6, 64, 3])), dtype=torch.float64, device=gpu), z, z,
+        ev.evaluate(torch.zeros((4, gene_count([6, 64, 3])), dtype=torch.float64, device=gpu), z, z,
                     torch.ones((4, 6), dtype=torch.float64, device=gpu), trace_games=1, trace_cap=8)

@@ -7,19 +7,17 @@ Checkers: the reference's own numbers (tests/golden/relu_forward.npz,
 relu_evaluate.json, written by tests/golden/make_relu_golden.py), the numpy
 loop (oracle/numpy_loop.py with its activation replaced by np.maximum(0.0, .))
 for the exact path, and the exact path for the hot one."""
-import importlib
 import random
 
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _dev_genomes, _gene_count
+from _gpu_support import HoF, Member, dev_genomes, dropin_config, gene_count, refused, same
 
 pytestmark = pytest.mark.gpu
 
 U32 = 2.0 ** -24
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 
 
 def _relu_ev(shape, gpu, **kw):
@@ -37,7 +35,7 @@ def test_forward_equals_reference(gpu, golden, key, precision):
     g = golden("relu_forward.npz")
     shape = [int(v) for v in g[f"{key}__shape"]]
     ev = _relu_ev(shape, gpu, precision=precision)
-    idx, act = ev.forward(_dev_genomes(g[f"{key}__genes"], gpu), _dev_genomes(g[f"{key}__x"], gpu),
+    idx, act = ev.forward(dev_genomes(g[f"{key}__genes"], gpu), dev_genomes(g[f"{key}__x"], gpu),
                           genome_index=torch.tensor(g[f"{key}__gidx"].astype(np.int32), device=gpu))
     np.testing.assert_array_equal(idx.cpu().numpy(), g[f"{key}__idx"])
     np.testing.assert_array_equal(act.cpu().numpy() + 0.0, g[f"{key}__act"] + 0.0)
@@ -88,7 +86,7 @@ def test_general_kernel_equals_numpy_loop(gpu, oracle, monkeypatch, shape):
 
     monkeypatch.setattr(NL.NumpyNet, "run", run)
     rng = np.random.default_rng(sum(shape))
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 8, 3
     genomes, opponents = rng.standard_normal((n, G)), rng.standard_normal((H, G))
     kinds = np.tile(np.array([0, 1, 2, 3, 3, 3], np.int32), (n, 1))
@@ -97,8 +95,8 @@ def test_general_kernel_equals_numpy_loop(gpu, oracle, monkeypatch, shape):
     mult[:, 3:] = np.round(rng.normal(size=(n, 3)), 3)
     mult[0, 3] = -0.625
     ev = _relu_ev(shape, gpu, kernel="general", timeout_thresh=119, win_score=1)
-    res, _ = ev.evaluate(_dev_genomes(genomes, gpu), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
-                         torch.tensor(mult, device=gpu), opponents=_dev_genomes(opponents, gpu))
+    res, _ = ev.evaluate(dev_genomes(genomes, gpu), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
+                         torch.tensor(mult, device=gpu), opponents=dev_genomes(opponents, gpu))
     torch.cuda.synchronize()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", RuntimeWarning)  # find_stuff's mean of an absent colour
@@ -111,12 +109,6 @@ def test_general_kernel_equals_numpy_loop(gpu, oracle, monkeypatch, shape):
 
 
 # -------------------------------- 3 games, the hot path against the exact ----
-def _same(a, b, n=None):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert torch.equal(x[:n], y[:n]), name
-
-
 @pytest.mark.parametrize("shape,dist,dtype", [([6, 64, 3], "n1", torch.float64), ([6, 16, 2], "init", torch.float64),
                                               ([6, 200, 4], "n1", torch.float32)])
 def test_relu_kernel_equals_general(gpu, shape, dist, dtype):
@@ -125,10 +117,10 @@ def test_relu_kernel_equals_general(gpu, shape, dist, dtype):
     counters equal the general kernel's; also through genome_rows (a
     permutation) with n_active below n."""
     rng = np.random.default_rng(sum(shape))
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 1024, 64
     draw = (lambda s: rng.random(s)) if dist == "init" else (lambda s: rng.standard_normal(s))
-    genomes, opponents = _dev_genomes(draw((n, G)), gpu, dtype), _dev_genomes(draw((H, G)), gpu, dtype)
+    genomes, opponents = dev_genomes(draw((n, G)), gpu, dtype), dev_genomes(draw((H, G)), gpu, dtype)
     kinds = np.tile(np.array([0, 1, 2, 3, 3, 3], np.int32), (n, 1))
     kinds[n // 2:] = 3
     opp = rng.integers(0, H, size=(n, 6)).astype(np.int32)
@@ -140,7 +132,7 @@ def test_relu_kernel_equals_general(gpu, shape, dist, dtype):
         got[kernel] = ev.evaluate(genomes, *sched, opponents=opponents, kernel=kernel, trace_games=64, trace_cap=2048)
     torch.cuda.synchronize()
     (hot, hot_tr), (ref, ref_tr), (auto, _) = got["relu"], got["general"], got["auto"]
-    _same(hot, ref)
+    same(hot, ref)
     assert torch.equal(hot_tr, ref_tr) and int(hot_tr.any())
     ch, cr, ca = (r.counters.cpu().numpy() for r in (hot, ref, auto))
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all()
@@ -155,8 +147,8 @@ def test_relu_kernel_equals_general(gpu, shape, dist, dtype):
     ref2, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="general", rows=perm, n_active=act)
     whole, _ = ev.evaluate(genomes[perm.long()].contiguous(), *sched, opponents=opponents, kernel="relu")
     torch.cuda.synchronize()
-    _same(hot2, ref2, 700)
-    _same(hot2, whole, 700)
+    same(hot2, ref2, 700)
+    same(hot2, whole, 700)
     assert int(hot2.counters[3]) == 700 * 6 == int(ref2.counters[3])
 
 
@@ -168,10 +160,10 @@ def _s_max(shape, g):
 
 
 def _decide_both(ev, gpu, genomes, k, gidx):
-    gt, kt = _dev_genomes(genomes, gpu), torch.tensor(k.astype(np.int32), device=gpu)
+    gt, kt = dev_genomes(genomes, gpu), torch.tensor(k.astype(np.int32), device=gpu)
     it = torch.tensor(gidx.astype(np.int32), device=gpu)
     index, stage, z32, bound = ev.relu_decide(gt, kt, genome_index=it)
-    ref_idx, _ = ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_layers=True)
+    ref_idx, _ = ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_layers=True)
     z64 = ev.last_layers[0][:, -ev.nodes[-1]:]
     torch.cuda.synchronize()
     return tuple(t.cpu().numpy() for t in (index, stage, z32, bound, ref_idx, z64))
@@ -183,7 +175,7 @@ def test_relu_decide_random_passes(gpu):
     max_o S_o, ~400 times the bound the derivation allows) is certified in f32."""
     shape = [6, 64, 3]
     rng = np.random.default_rng(4)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     genomes = rng.standard_normal((64, G))
     genomes[:16] = rng.random((16, G))
     k = rng.integers(0, 321, size=(64 * 512, 6))
@@ -240,7 +232,7 @@ def test_relu_decide_near_ties_zero_boundary_and_huge_weights(gpu):
     assert (index[gidx == 0] == 2).all() and (index[gidx == 1] == 0).all() and (stage == 1).all()
     # (d) a weight f32 sums cannot hold: bound inf, always the f64 forward
     shape = [6, 64, 3]
-    g = rng.standard_normal((2, _gene_count(shape)))
+    g = rng.standard_normal((2, gene_count(shape)))
     g[0, 5] = 1e30
     g[1, 64 * 7 + 3] = -1e30
     k = rng.integers(0, 321, size=(128, 6))
@@ -252,30 +244,24 @@ def test_relu_decide_near_ties_zero_boundary_and_huge_weights(gpu):
 
 # ------------------------------------------------------------ 5 unsupported ----
 def test_unsupported_combinations_are_refused(gpu):
-    from pong_amd import _lib
     from pong_amd.device import Evaluator
     shape = [6, 64, 3]
-    G = _gene_count(shape)
+    G = gene_count(shape)
     genomes = torch.zeros((4, G), dtype=torch.float64, device=gpu)
     z = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
     m = torch.ones((4, 6), dtype=torch.float64, device=gpu)
     k = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
 
-    def refused(fn, word="relu"):
-        with pytest.raises(_lib.PongGAError) as e:
-            fn()
-        assert e.value.code == _lib.PG_ERR_UNSUPPORTED and word in str(e.value), str(e.value)
-
     ev = _relu_ev(shape, gpu)
-    refused(lambda: ev.evaluate(genomes, z, z, m, kernel="split"))
-    refused(lambda: ev.evaluate(genomes, z, z, m, horizon=1000))
-    refused(lambda: ev.evaluate(genomes, z, z, m, hard_log=torch.zeros((8, 8), dtype=torch.int32, device=gpu)))
-    refused(lambda: ev.decide(genomes, k))
+    refused(lambda: ev.evaluate(genomes, z, z, m, kernel="split"), "relu")
+    refused(lambda: ev.evaluate(genomes, z, z, m, horizon=1000), "relu")
+    refused(lambda: ev.evaluate(genomes, z, z, m, hard_log=torch.zeros((8, 8), dtype=torch.int32, device=gpu)), "relu")
+    refused(lambda: ev.decide(genomes, k), "relu")
     wide = _relu_ev([6, 64, 64, 3], gpu, dtype=torch.float32)
     gw = torch.zeros((4, wide.genes), dtype=torch.float32, device=gpu)
-    refused(lambda: wide.evaluate(gw, z, z, m, kernel="wide"))
-    refused(lambda: wide.wide_decide(gw, k))
-    refused(lambda: wide.evaluate(gw, z, z, m, kernel="relu"))  # outside k_relu's shapes
+    refused(lambda: wide.evaluate(gw, z, z, m, kernel="wide"), "relu")
+    refused(lambda: wide.wide_decide(gw, k), "relu")
+    refused(lambda: wide.evaluate(gw, z, z, m, kernel="relu"), "relu")  # outside k_relu's shapes
     refused(lambda: _relu_ev(shape, gpu, precision="f64").evaluate(genomes, z, z, m, kernel="relu"), "certified")
     sig = Evaluator(shape, device=gpu)
     refused(lambda: sig.evaluate(genomes, z, z, m, kernel="relu"), "sigmoid")
@@ -286,37 +272,13 @@ def test_unsupported_combinations_are_refused(gpu):
 
 
 # ---------------------------------------------------------------- 6 drop-in ----
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.fixture
 def relu_dropin():
     """config.ACTIVATION = "relu" as a user sets it: numpy_nn initialises its
     activation_function from the knob when it is imported."""
-    import config
-    import numpy_nn
-    saved = config.ACTIVATION
-    config.ACTIVATION = "relu"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="relu"):
+        import numpy_nn
         yield numpy_nn
-    finally:
-        config.ACTIVATION = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_matches_reference(gpu, golden, relu_dropin):
@@ -331,7 +293,7 @@ def test_dropin_evaluate_matches_reference(gpu, golden, relu_dropin):
         for case in golden("relu_evaluate.json"):
             assert len(set(case["fitness"])) >= 3 and min(case["hof_fitness"]) < 0
             utils.NETWORK_SHAPE = case["shape"]
-            main.hall_of_fame = _HoF([_Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])])
+            main.hall_of_fame = HoF([Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])])
             random.seed(case["random_seed"])
             inds = [list(g) for g in case["individuals"]]
             got = [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]

@@ -5,25 +5,18 @@ layers, [6, 2..64, 2..64, 2..4] with bias, on the certified f32 game kernel
 Checkers: the reference's own numbers (tests/golden/relu_forward.npz), pg_forward
 in f64 for single decisions, and the general kernel for whole games
 (tests/test_gpu_relu.py pins it to the reference's numpy loop at [6,5,4,2])."""
-import importlib
-import random
 
 import numpy as np
 import pytest
 import torch
 
 import _relu2_model as M
-from test_gpu_parity import _dev_genomes
+from _gpu_support import dev_genomes, dropin_config, dropin_fitness, ids, refused, same
 
 pytestmark = pytest.mark.gpu
 
 U32 = 2.0 ** -24
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 DTYPES = [torch.float64, torch.float32]
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, list) else str(v).replace("torch.", "")
 
 
 def _relu_ev(shape, gpu, **kw):
@@ -33,10 +26,10 @@ def _relu_ev(shape, gpu, **kw):
 
 def _decide_both(ev, gpu, genomes, k, gidx):
     """relu2_decide and the f64 pg_forward on the same passes (genomes as ev's dtype holds them)."""
-    gt, kt = _dev_genomes(genomes, gpu, ev.dtype), torch.tensor(k.astype(np.int32), device=gpu)
+    gt, kt = dev_genomes(genomes, gpu, ev.dtype), torch.tensor(k.astype(np.int32), device=gpu)
     it = torch.tensor(gidx.astype(np.int32), device=gpu)
     index, stage, z32, bound = ev.relu2_decide(gt, kt, genome_index=it)
-    ref_idx, _ = ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_layers=True)
+    ref_idx, _ = ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_layers=True)
     z64 = ev.last_layers[0][:, -ev.nodes[-1]:]
     torch.cuda.synchronize()
     return tuple(t.cpu().numpy() for t in (index, stage, z32, bound, ref_idx, z64))
@@ -59,15 +52,15 @@ def test_decide_equals_reference(gpu, golden):
     sel = np.flatnonzero(((k / 2) / 160 == x).all(axis=1) & (k >= 0).all(axis=1) & (k <= 320).all(axis=1))
     assert len(sel) == len(x) // 2
     ev = _relu_ev(shape, gpu)
-    index, stage, _, bound = ev.relu2_decide(_dev_genomes(g[f"{key}__genes"], gpu), torch.tensor(k[sel].astype(np.int32), device=gpu),
+    index, stage, _, bound = ev.relu2_decide(dev_genomes(g[f"{key}__genes"], gpu), torch.tensor(k[sel].astype(np.int32), device=gpu),
                                              genome_index=torch.tensor(g[f"{key}__gidx"][sel].astype(np.int32), device=gpu))
     np.testing.assert_array_equal(index.cpu().numpy(), g[f"{key}__idx"][sel])
     assert set(np.unique(stage.cpu().numpy())) <= {0, 1} and np.isfinite(bound.cpu().numpy()).all()
 
 
 # ------------------------------------------------------- 2 random passes ----
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
-@pytest.mark.parametrize("shape", M.SHAPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+@pytest.mark.parametrize("shape", M.LANES.SHAPES, ids=ids)
 def test_decide_random_passes(gpu, shape, dtype):
     """64 networks x 512 inputs: the decision is the f64 forward's, |z32 - z64|
     stays within the (finite) bound, z32 is the host model's chain bit for bit,
@@ -86,7 +79,7 @@ def test_decide_random_passes(gpu, shape, dtype):
     assert np.isfinite(bound).all()
     assert (np.abs(z32.astype(np.float64) - z64) <= bound[:, None]).all()
     s = M.s_max(shape, genomes)[gidx]
-    assert (bound <= 2 * M.RELU2_K * U32 * s).all()
+    assert (bound <= 2 * M.LANES.K * U32 * s).all()
     large = _margin(z64) > 1e-3 * s
     assert set(np.unique(stage)) <= {0, 1}
     print(f"{shape} {dtype}: stage-1 share {np.mean(stage == 1):.5f} of {len(stage)} passes "
@@ -96,7 +89,7 @@ def test_decide_random_passes(gpu, shape, dtype):
     assert np.mean(stage == 1) <= 0.05
     # the f32 chain is the documented one: the host model's z32 on the first 8 inputs of every network
     sub = (np.arange(64)[:, None] * 512 + np.arange(8)[None, :]).ravel()
-    want = M.z32(shape, genomes, k[sub].reshape(64, 8, 6)).reshape(-1, shape[-1])
+    want = M.z32(M.LANES, shape, genomes, k[sub].reshape(64, 8, 6)).reshape(-1, shape[-1])
     np.testing.assert_array_equal(z32[sub].view(np.int32), want.view(np.int32))
 
 
@@ -118,7 +111,7 @@ def _tie_nets(shape, rng, deltas):
     return np.array(nets)
 
 
-@pytest.mark.parametrize("shape", [[6, 16, 16, 3], [6, 17, 33, 4], [6, 64, 64, 3], [6, 20, 32, 4]], ids=_ids)
+@pytest.mark.parametrize("shape", [[6, 16, 16, 3], [6, 17, 33, 4], [6, 64, 64, 3], [6, 20, 32, 4]], ids=ids)
 def test_decide_hard_inputs(gpu, shape):
     _, H1, H2, O = shape
     rng = np.random.default_rng(5 + sum(shape))
@@ -169,12 +162,6 @@ def test_decide_hard_inputs(gpu, shape):
 
 
 # --------------------------------------------------------- 4 whole games ----
-def _same(a, b, n=None):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert torch.equal(x[:n], y[:n]), name
-
-
 def _f64_rows(shape, rng, n):
     """n genomes that always need the f64 path: tie, 1e30, all-zero and NaN, in turn (f32 values throughout)."""
     _, H1, H2, O = shape
@@ -196,8 +183,8 @@ def _f64_rows(shape, rng, n):
     return np.array(rows).astype(np.float32).astype(np.float64)
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
-@pytest.mark.parametrize("shape", M.SHAPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+@pytest.mark.parametrize("shape", M.LANES.SHAPES, ids=ids)
 def test_relu2_kernel_equals_general(gpu, shape, dtype):
     """k_relu2's certified decisions are the f64 forward's: every output array,
     the per-frame traces of the first 64 games and the step / forward / game
@@ -207,7 +194,7 @@ def test_relu2_kernel_equals_general(gpu, shape, dtype):
     rng = np.random.default_rng(sum(shape) + 1)
     G = M.genes(shape)
     n, H = 256, 16
-    genomes, opponents = _dev_genomes(rng.standard_normal((n, G)), gpu, dtype), _dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
+    genomes, opponents = dev_genomes(rng.standard_normal((n, G)), gpu, dtype), dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
     kinds = np.tile(np.array([0, 1, 2, 3, 3, 3], np.int32), (n, 1))
     kinds[n // 2:] = 3
     opp = rng.integers(0, H, size=(n, 6)).astype(np.int32)
@@ -220,7 +207,7 @@ def test_relu2_kernel_equals_general(gpu, shape, dtype):
         got[kernel] = ev.evaluate(genomes, *sched, opponents=opponents, kernel=kernel, trace_games=64, trace_cap=2048)
     torch.cuda.synchronize()
     (hot, hot_tr), (ref, ref_tr), (auto, _) = got["relu2"], got["general"], got["auto"]
-    _same(hot, ref)
+    same(hot, ref)
     assert torch.equal(hot_tr, ref_tr) and int(hot_tr.any())
     ch, cr, ca = (r.counters.cpu().numpy() for r in (hot, ref, auto))
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all()
@@ -229,12 +216,12 @@ def test_relu2_kernel_equals_general(gpu, shape, dtype):
     assert ch[2] == ch[4] <= 0.25 * ch[1]
     assert (ca == ch).all()  # AUTO resolves to k_relu2 in its scope
     # genomes and opponents that always need the f64 path
-    hard, hard_opp = _dev_genomes(_f64_rows(shape, rng, 64), gpu, dtype), _dev_genomes(_f64_rows(shape, rng, H), gpu, dtype)
+    hard, hard_opp = dev_genomes(_f64_rows(shape, rng, 64), gpu, dtype), dev_genomes(_f64_rows(shape, rng, H), gpu, dtype)
     hsched = [t[:64].contiguous() for t in sched]
     hot_h, tr_h = ev.evaluate(hard, *hsched, opponents=hard_opp, kernel="relu2", trace_games=64, trace_cap=2048)
     ref_h, rtr_h = ev.evaluate(hard, *hsched, opponents=hard_opp, kernel="general", trace_games=64, trace_cap=2048)
     torch.cuda.synchronize()
-    _same(hot_h, ref_h)
+    same(hot_h, ref_h)
     assert torch.equal(tr_h, rtr_h)
     chh = hot_h.counters.cpu().numpy()
     assert (chh[[0, 1, 3]] == ref_h.counters.cpu().numpy()[[0, 1, 3]]).all() and chh[2] == chh[4] == chh[1]
@@ -245,13 +232,13 @@ def test_relu2_kernel_equals_general(gpu, shape, dtype):
     ref2, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="general", rows=perm, n_active=act)
     whole, _ = ev.evaluate(genomes[perm.long()].contiguous(), *sched, opponents=opponents, kernel="relu2")
     torch.cuda.synchronize()
-    _same(hot2, ref2, 170)
-    _same(hot2, whole, 170)
+    same(hot2, ref2, 170)
+    same(hot2, whole, 170)
     assert int(hot2.counters[3]) == 170 * 6 == int(ref2.counters[3])
 
 
 @pytest.mark.parametrize("shape,n,dtype", [([6, 16, 16, 3], 4096, torch.float64), ([6, 20, 32, 4], 1024, torch.float32),
-                                           ([6, 64, 64, 3], 1024, torch.float64)], ids=_ids)
+                                           ([6, 64, 64, 3], 1024, torch.float64)], ids=ids)
 def test_relu2_groups_play_several_games(gpu, shape, n, dtype):
     """More games than the launch has lane groups (2 blocks per CU of 32, 8 or 4
     groups), so every group takes further games from the queue and replaces its
@@ -262,7 +249,7 @@ def test_relu2_groups_play_several_games(gpu, shape, n, dtype):
     groups = 2 * torch.cuda.get_device_properties(gpu).multi_processor_count * (256 // (2 * LN))
     assert n * 6 > 1.4 * groups
     H = 64
-    genomes, opponents = _dev_genomes(rng.standard_normal((n, G)), gpu, dtype), _dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
+    genomes, opponents = dev_genomes(rng.standard_normal((n, G)), gpu, dtype), dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
     kinds = np.tile(np.array([0, 1, 2, 3, 3, 3], np.int32), (n, 1))
     kinds[n // 2:] = 3
     sched = [torch.tensor(a, device=gpu) for a in (kinds, rng.integers(0, H, size=(n, 6)).astype(np.int32),
@@ -271,12 +258,12 @@ def test_relu2_groups_play_several_games(gpu, shape, n, dtype):
     hot, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="relu2")
     ref, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="general")
     torch.cuda.synchronize()
-    _same(hot, ref)
+    same(hot, ref)
     ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all() and ch[3] == n * 6 and ch[2] == ch[4] <= 0.25 * ch[1]
 
 
-@pytest.mark.parametrize("shape", [[6, 2, 2, 2], [6, 17, 3, 3], [6, 33, 64, 4]], ids=_ids)
+@pytest.mark.parametrize("shape", [[6, 2, 2, 2], [6, 17, 3, 3], [6, 33, 64, 4]], ids=ids)
 def test_relu2_counter_flush(gpu, shape):
     """The shared game loop's flush of a family whose stages are 0/1: one
     count of f64 forwards goes to both [2] and [4].  The smallest padded shape
@@ -284,8 +271,8 @@ def test_relu2_counter_flush(gpu, shape):
     that both half-groups play; half of the rows always need the f64 path."""
     rng = np.random.default_rng(sum(shape) + 3)
     G = M.genes(shape)
-    genomes = _dev_genomes(np.concatenate([rng.standard_normal((4, G)), _f64_rows(shape, rng, 4)]), gpu, torch.float64)
-    hall = _dev_genomes(np.concatenate([rng.standard_normal((2, G)), _f64_rows(shape, rng, 2)]), gpu, torch.float64)
+    genomes = dev_genomes(np.concatenate([rng.standard_normal((4, G)), _f64_rows(shape, rng, 4)]), gpu, torch.float64)
+    hall = dev_genomes(np.concatenate([rng.standard_normal((2, G)), _f64_rows(shape, rng, 2)]), gpu, torch.float64)
     sched = [torch.tensor(a, device=gpu) for a in (np.full((8, 2), 3, np.int32), rng.integers(0, 4, size=(8, 2)).astype(np.int32),
                                                    np.ones((8, 2)))]
     ev = _relu_ev(shape, gpu, n_games=2, timeout_thresh=119, win_score=1)
@@ -297,7 +284,6 @@ def test_relu2_counter_flush(gpu, shape):
 
 # ------------------------------------------------------------ 5 refusals ----
 def test_unsupported_combinations_are_refused(gpu):
-    from pong_amd import _lib
     from pong_amd.device import Evaluator
     shape = [6, 64, 64, 3]
     z = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
@@ -306,11 +292,6 @@ def test_unsupported_combinations_are_refused(gpu):
 
     def genomes(ev):
         return torch.zeros((4, ev.genes), dtype=torch.float64, device=gpu)
-
-    def refused(fn, word="relu"):
-        with pytest.raises(_lib.PongGAError) as e:
-            fn()
-        assert e.value.code == _lib.PG_ERR_UNSUPPORTED and word in str(e.value), str(e.value)
 
     ev = _relu_ev(shape, gpu)
     g = genomes(ev)
@@ -327,10 +308,10 @@ def test_unsupported_combinations_are_refused(gpu):
     refused(lambda: ev.evaluate(g, z, z, m, kernel="relu2", horizon=1000), "horizon")
     refused(lambda: ev.evaluate(g, z, z, m, kernel="relu2", hard_log=torch.zeros((8, 8), dtype=torch.int32, device=gpu)),
             "hard")
-    refused(lambda: ev.evaluate(g, z, z, m, kernel="relu"))  # outside k_relu's shapes
-    refused(lambda: ev.evaluate(g, z, z, m, kernel="wide"))
-    refused(lambda: ev.wide_decide(g, k))
-    refused(lambda: ev.relu_decide(g, k))
+    refused(lambda: ev.evaluate(g, z, z, m, kernel="relu"), "relu")  # outside k_relu's shapes
+    refused(lambda: ev.evaluate(g, z, z, m, kernel="wide"), "relu")
+    refused(lambda: ev.wide_decide(g, k), "relu")
+    refused(lambda: ev.relu_decide(g, k), "relu")
     # the supported neighbours of the refused calls still run
     for kernel in ("relu2", "auto", "general"):
         res, _ = ev.evaluate(g, z, z, m, kernel=kernel)
@@ -379,44 +360,19 @@ def test_device_ga_relu2_generations_and_checkpoint(gpu, tmp_path):
     assert torch.equal(ga.population_full(), ga2.population_full()) and torch.equal(ga.fitness, ga2.fitness)
 
 
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.fixture
 def relu_dropin():
     """config.ACTIVATION = "relu" as a user sets it: numpy_nn initialises its
     activation_function from the knob when it is imported."""
-    import config
-    import numpy_nn
-    saved = config.ACTIVATION
-    config.ACTIVATION = "relu"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="relu"):
+        import numpy_nn
         yield numpy_nn
-    finally:
-        config.ACTIVATION = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_equals_general(gpu, relu_dropin, monkeypatch):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on a [6,16,16,2] ReLU network
     (AUTO: k_relu2) against the same call with the evaluator held to the
     general kernel: the same hall, the same random seed, the same fitness."""
-    import ga
     import main
     import utils
     assert relu_dropin.activation() == "relu"
@@ -429,17 +385,12 @@ def test_dropin_evaluate_equals_general(gpu, relu_dropin, monkeypatch):
         hall = rng.standard_normal((4, G))
         inds = [list(g) for g in rng.standard_normal((24, G))]
 
-        def fitness():  # (pick_hall_of_famer shuffles the hall in place: a fresh one, in the same order, per run)
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
-
         ev = main._evaluator()
         assert ev.activation == "relu" and list(ev.nodes) == shape and ev.kernel == "auto"
-        got = fitness()
+        got = dropin_fitness(hall, inds)
         monkeypatch.setattr(ev, "kernel", "general")
         assert main._evaluator() is ev
-        want = fitness()
+        want = dropin_fitness(hall, inds)
         assert got == want and len(set(got)) >= 3
     finally:
         utils.NETWORK_SHAPE, main.hall_of_fame = saved

@@ -5,29 +5,22 @@ pg_relu2_block_decide pins its decisions).
 
 Checkers: numpy's own forward (np.dot per layer, as NeuralNetwork.run does) and
 pg_forward in f64 for single decisions, the host model of the f32 chain
-(tests/_relu2_block_model.py) for z32, the gcc-compiled bound, the general
+(tests/_relu2_model.py, its BLOCK layout) for z32, the gcc-compiled bound, the general
 kernel for whole games and k_relu2 on the shapes both kernels take.  All games
 run with timeout_thresh=119, win_score=1."""
-import importlib
-import random
 
 import numpy as np
 import pytest
 import torch
 
-import _relu2_block_model as M
-from test_gpu_parity import _dev_genomes
+import _relu2_model as M
+from _gpu_support import dev_genomes, dropin_config, dropin_fitness, ids, refused, same
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 DTYPES = [torch.float64, torch.float32]
 EDGE_SHAPES = [[6, 2, 2, 2], [6, 65, 2, 2], [6, 2, 65, 3], [6, 100, 100, 3], [6, 128, 128, 4]]
 GAME_SHAPES = [[6, 65, 2, 2], [6, 100, 100, 3], [6, 128, 128, 4]]
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, list) else str(v).replace("torch.", "")
 
 
 def _ev(shape, gpu, **kw):
@@ -37,12 +30,12 @@ def _ev(shape, gpu, **kw):
 
 def _decide(ev, gpu, genomes, k, gidx, forward=True):
     """relu2_block_decide (and the f64 pg_forward's index) on passes k [n, 6] of genomes[gidx]."""
-    gt, kt = _dev_genomes(genomes, gpu, ev.dtype), torch.tensor(k.astype(np.int32), device=gpu)
+    gt, kt = dev_genomes(genomes, gpu, ev.dtype), torch.tensor(k.astype(np.int32), device=gpu)
     it = torch.tensor(gidx.astype(np.int32), device=gpu)
     index, stage, z32, bound = ev.relu2_block_decide(gt, kt, genome_index=it)
     out = [index, stage, z32, bound]
     if forward:
-        out.append(ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64")[0])
+        out.append(ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64")[0])
     torch.cuda.synchronize()
     return tuple(t.cpu().numpy() for t in out)
 
@@ -56,8 +49,8 @@ def _one_ulp32(got, want):
 
 
 # ------------------------------------------------------- 1 random passes ----
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
-@pytest.mark.parametrize("shape", M.SHAPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+@pytest.mark.parametrize("shape", M.BLOCK.SHAPES, ids=ids)
 def test_decide_random_passes(gpu, tmp_path, shape, dtype):
     """64 networks (U[0,1), N(0,1) and N(0,3) genes) x 64 inputs = 4 096 passes:
     z32 is the host model's chain bit for bit, the bound the gcc-compiled one to
@@ -72,9 +65,9 @@ def test_decide_random_passes(gpu, tmp_path, shape, dtype):
     k = rng.integers(0, 321, size=(64, 64, 6))
     gidx = np.repeat(np.arange(64), 64)
     index, stage, z32, bound, fwd = _decide(_ev(shape, gpu, dtype=dtype), gpu, genomes, k.reshape(-1, 6), gidx)
-    want = M.z32(shape, genomes, k).reshape(-1, shape[-1])
+    want = M.z32(M.BLOCK, shape, genomes, k).reshape(-1, shape[-1])
     np.testing.assert_array_equal(z32.view(np.int32), want.view(np.int32))
-    _one_ulp32(bound, M.bounds(tmp_path, shape, genomes)[gidx])
+    _one_ulp32(bound, M.bounds(tmp_path, M.BLOCK, shape, genomes)[gidx])
     assert np.isfinite(bound).all() and set(np.unique(stage)) <= {0, 1}
     np.testing.assert_array_equal(index, M.numpy_index(shape, genomes, k).ravel())
     np.testing.assert_array_equal(index, fwd)
@@ -85,7 +78,7 @@ def test_decide_random_passes(gpu, tmp_path, shape, dtype):
 
 # ------------------------------------- 2 the certificate must do the work ----
 @pytest.mark.parametrize("law", ["normal1", "normal3", "uniform"])
-@pytest.mark.parametrize("shape", M.SHAPES, ids=_ids)
+@pytest.mark.parametrize("shape", M.BLOCK.SHAPES, ids=ids)
 def test_certificate_decides_most_passes(gpu, shape, law):
     """An e = inf bug would pass every equality above: per shape and gene law
     the share of passes decided by the f32 certificate (stage 0) is at least
@@ -134,7 +127,7 @@ def _bias_delta(shape, rng, base=None):
     return base
 
 
-@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=_ids)
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=ids)
 def test_decide_built_cases(gpu, shape):
     _, H1, H2, O = shape
     rng = np.random.default_rng(60 + sum(shape))
@@ -160,7 +153,7 @@ def test_decide_built_cases(gpu, shape):
     assert (stage == 1).all() and np.isfinite(bound).all()
     # (b) a bias difference delta around 2e: certified beyond it, f64 within it
     base = _bias_delta(shape, rng)
-    e = float(M.bound_numpy(shape, base[None])[0])
+    e = float(M.bound_numpy(M.BLOCK, shape, base[None])[0])
     factors = np.array([0.0, 0.5, -0.5, 1.5, -1.5, 1.9, -1.9, 2.1, -2.1, 2.5, -2.5, 8.0, -8.0])
     nets = np.tile(base, (len(factors), 1))
     bias1 = b + (H2 + 1) + H2
@@ -205,12 +198,6 @@ def test_decide_built_cases(gpu, shape):
 
 
 # --------------------------------------------------------- 4 whole games ----
-def _same(a, b, n=None):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert torch.equal(x[:n], y[:n]), name
-
-
 def _hard_rows(shape, rng):
     """A genome whose every forward needs f64 (a tie network), a NaN genome and a 1e30 genome (f32 values)."""
     G = M.genes(shape)
@@ -223,11 +210,11 @@ def _hard_rows(shape, rng):
 def _population(shape, rng, n, gpu, dtype):
     g = rng.standard_normal((n, M.genes(shape)))
     g[:3] = _hard_rows(shape, rng)
-    return _dev_genomes(g, gpu, dtype)
+    return dev_genomes(g, gpu, dtype)
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
-@pytest.mark.parametrize("shape", GAME_SHAPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+@pytest.mark.parametrize("shape", GAME_SHAPES, ids=ids)
 def test_kernel_equals_general(gpu, shape, dtype):
     """48 genomes x 6 games on the reference schedule and all self-play, with a
     genome whose every forward needs f64, a NaN and a 1e30 genome among genomes
@@ -246,7 +233,7 @@ def test_kernel_equals_general(gpu, shape, dtype):
         hot, hot_tr = ev.evaluate(genomes, *sched, opponents=hall, kernel="relu2_block", trace_games=n * 6, trace_cap=1024)
         ref, ref_tr = ev.evaluate(genomes, *sched, opponents=hall, kernel="general", trace_games=n * 6, trace_cap=1024)
         torch.cuda.synchronize()
-        _same(hot, ref)
+        same(hot, ref)
         assert torch.equal(hot_tr, ref_tr) and int(hot_tr.any())
         ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
         assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all()
@@ -259,8 +246,8 @@ def test_kernel_equals_general(gpu, shape, dtype):
     ref2, _ = ev.evaluate(genomes, *sched, opponents=hall, kernel="general", rows=perm, n_active=act)
     whole, _ = ev.evaluate(genomes[perm.long()].contiguous(), *sched, opponents=hall, kernel="relu2_block")
     torch.cuda.synchronize()
-    _same(hot2, ref2, 31)
-    _same(hot2, whole, 31)
+    same(hot2, ref2, 31)
+    same(hot2, whole, 31)
     assert int(hot2.counters[3]) == 31 * 6 == int(ref2.counters[3])
 
 
@@ -284,13 +271,13 @@ def test_blocks_reload_games_in_place(gpu):
     hot, _ = ev.evaluate(genomes, *sched, opponents=hall, kernel="relu2_block")
     ref, _ = ev.evaluate(genomes, *sched, opponents=hall, kernel="general")
     torch.cuda.synchronize()
-    _same(hot, ref)
+    same(hot, ref)
     ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
     assert ch[3] == n * 6 and ch[0] == int(hot.frames.sum()) and (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all()
     assert ch[8] == 0 and ch[12] == 0
 
 
-@pytest.mark.parametrize("shape", [[6, 16, 16, 3], [6, 64, 64, 3]], ids=_ids)
+@pytest.mark.parametrize("shape", [[6, 16, 16, 3], [6, 64, 64, 3]], ids=ids)
 def test_overlap_with_relu2(gpu, shape):
     """On the shapes k_relu2 takes too, the outputs and the steps / forwards /
     games counters are k_relu2's."""
@@ -304,7 +291,7 @@ def test_overlap_with_relu2(gpu, shape):
     hot, hot_tr = ev.evaluate(genomes, *sched, opponents=hall, kernel="relu2_block", trace_games=64, trace_cap=1024)
     ref, ref_tr = ev.evaluate(genomes, *sched, opponents=hall, kernel="relu2", trace_games=64, trace_cap=1024)
     torch.cuda.synchronize()
-    _same(hot, ref)
+    same(hot, ref)
     assert torch.equal(hot_tr, ref_tr)
     ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all() and ch[3] == n * 6
@@ -312,7 +299,6 @@ def test_overlap_with_relu2(gpu, shape):
 
 # ------------------------------------------------------------ 5 refusals ----
 def test_unsupported_combinations_are_refused(gpu):
-    from pong_amd import _lib
     from pong_amd.device import Evaluator
     shape = [6, 128, 128, 3]
     z = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
@@ -321,11 +307,6 @@ def test_unsupported_combinations_are_refused(gpu):
 
     def genomes(ev):
         return torch.zeros((4, ev.genes), dtype=torch.float64, device=gpu)
-
-    def refused(fn, word="relu2_block"):
-        with pytest.raises(_lib.PongGAError) as e:
-            fn()
-        assert e.value.code == _lib.PG_ERR_UNSUPPORTED and word in str(e.value), str(e.value)
 
     ev = _ev(shape, gpu)
     g = genomes(ev)
@@ -382,43 +363,18 @@ def test_device_ga_generations_and_checkpoint(gpu, tmp_path):
         assert torch.equal(ga.population_full(), other.population_full()) and torch.equal(ga.fitness, other.fitness)
 
 
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.fixture
 def relu_dropin():
     """config.ACTIVATION = "relu" and config.KERNEL = "relu2_block" as a user sets them."""
-    import config
-    import numpy_nn
-    saved = (config.ACTIVATION, config.KERNEL)
-    config.ACTIVATION, config.KERNEL = "relu", "relu2_block"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="relu", kernel="relu2_block"):
+        import numpy_nn
         yield numpy_nn
-    finally:
-        config.ACTIVATION, config.KERNEL = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_equals_general(gpu, relu_dropin, monkeypatch):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on a [6,100,100,2] ReLU network
     with config.KERNEL = "relu2_block" against the same call with the evaluator
     held to the general kernel: the same hall, the same random seed, the same fitness."""
-    import ga
     import main
     import utils
     assert relu_dropin.activation() == "relu"
@@ -431,17 +387,12 @@ def test_dropin_evaluate_equals_general(gpu, relu_dropin, monkeypatch):
         hall = rng.standard_normal((4, G))
         inds = [list(g) for g in rng.standard_normal((12, G))]
 
-        def fitness():  # (pick_hall_of_famer shuffles the hall in place: a fresh one, in the same order, per run)
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
-
         ev = main._evaluator()
         assert ev.activation == "relu" and list(ev.nodes) == shape and ev.kernel == "relu2_block"
-        got = fitness()
+        got = dropin_fitness(hall, inds)
         monkeypatch.setattr(ev, "kernel", "general")
         assert main._evaluator() is ev
-        want = fitness()
+        want = dropin_fitness(hall, inds)
         assert got == want and len(set(got)) >= 3
     finally:
         utils.NETWORK_SHAPE, main.hall_of_fame = saved

@@ -17,11 +17,10 @@ import torch
 
 from _relu_model import (RELU_CAP, TIE_CELLS, U32, _argmax64, _bounds, _genes, _relu_lanes, _s_max, _z32, _z64,
                          cap_net, systematic_net, tie_case, tie_net, tie_sensitivity, tiny_net)
-from test_gpu_parity import _dev_genomes, _gene_count
+from _gpu_support import dev_genomes, gene_count, same
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 DTYPES = {"f32": torch.float32, "f64": torch.float64}
 
 
@@ -46,11 +45,11 @@ def _as_stored(genomes, dtype):
 
 def _decide(ev, gpu, genomes, k, gidx, dtype):
     """pg_relu_decide and pg_forward(f64) on the same passes, as numpy arrays."""
-    gt = _dev_genomes(genomes, gpu, DTYPES[dtype])
+    gt = dev_genomes(genomes, gpu, DTYPES[dtype])
     kt = torch.tensor(k.astype(np.int32), device=gpu)
     it = torch.tensor(gidx.astype(np.int32), device=gpu)
     index, stage, z32, bound = ev.relu_decide(gt, kt, genome_index=it)
-    ref_idx, act = ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64")
+    ref_idx, act = ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64")
     torch.cuda.synchronize()
     return tuple(t.cpu().numpy() for t in (index, stage, z32, bound, ref_idx, act))
 
@@ -82,7 +81,7 @@ def test_decide_is_the_host_model(gpu, bound_dir, H, O, dtype):
     summation orders can differ by, the index is numpy's."""
     rng = np.random.default_rng([H, O, dtype == "f32", 41])
     G = _genes(H, O)
-    assert G == _gene_count([6, H, O])
+    assert G == gene_count([6, H, O])
     nets = np.concatenate([rng.standard_normal((3, G)), rng.random((2, G)), systematic_net(H, O)[None]])
     nets = _as_stored(nets, dtype)
     per = 37
@@ -234,12 +233,6 @@ def _game_cases():
 PERMUTED = {(4, 3, "f64"), (8, 4, "f32"), (16, 2, "f64")}
 
 
-def _same(a, b, n=None):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert torch.equal(x[:n], y[:n]), name
-
-
 @pytest.mark.parametrize("LN,O,dtype,H", list(_game_cases()))
 def test_relu_games_every_instance(gpu, LN, O, dtype, H):
     """32 genomes x 6 games (scripted, ROM CPU, score-aware and hall-of-fame
@@ -271,14 +264,14 @@ def test_relu_games_every_instance(gpu, LN, O, dtype, H):
     opp = rng.integers(0, n_opp, size=(n, games)).astype(np.int32)
     mult = np.round(rng.normal(size=(n, games)), 3)
     assert (mult < 0).any() and (mult > 0).any()
-    gt, ot = _dev_genomes(genomes, gpu, DTYPES[dtype]), _dev_genomes(opponents, gpu, DTYPES[dtype])
+    gt, ot = dev_genomes(genomes, gpu, DTYPES[dtype]), dev_genomes(opponents, gpu, DTYPES[dtype])
     sched = [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
     ev = _relu_ev(shape, gpu, dtype=DTYPES[dtype], timeout_thresh=119, win_score=1)
     cap = 2048
     hot, hot_tr = ev.evaluate(gt, *sched, opponents=ot, kernel="relu", trace_games=n * games, trace_cap=cap)
     ref, ref_tr = ev.evaluate(gt, *sched, opponents=ot, kernel="general", trace_games=n * games, trace_cap=cap)
     torch.cuda.synchronize()
-    _same(hot, ref)
+    same(hot, ref)
     assert torch.equal(hot_tr, ref_tr) and int(hot_tr.any())
     ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all() and ch[3] == n * games
@@ -299,6 +292,6 @@ def test_relu_games_every_instance(gpu, LN, O, dtype, H):
         ref2, _ = ev.evaluate(gt, *sched, opponents=ot, kernel="general", rows=perm, n_active=act)
         whole, _ = ev.evaluate(gt[perm.long()].contiguous(), *sched, opponents=ot, kernel="relu")
         torch.cuda.synchronize()
-        _same(hot2, ref2, 19)
-        _same(hot2, whole, 19)
+        same(hot2, ref2, 19)
+        same(hot2, whole, 19)
         assert int(hot2.counters[3]) == 19 * games == int(ref2.counters[3])

@@ -17,8 +17,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_advance import DEFAULT, _ids, outcome_shares, population
-from test_gpu_parity import _dev_genomes, _gene_count
+from _gpu_support import dev_genomes, gene_count, ids
+from test_gpu_advance import DEFAULT, outcome_shares, population
 
 pytestmark = pytest.mark.gpu
 
@@ -44,7 +44,7 @@ def _population(shape, bias=True, n=N, hall=HALL):
     if min(shape[1:]) < 2:  # no room for the tracker's two units
         rng = np.random.default_rng(sum(shape))
         _, _, kinds, opp, mult = population([6, 2, 2], "relu", n=n, hall=hall, seed=sum(shape))
-        return rng.standard_normal((n, _gene_count(shape))), rng.standard_normal((hall, _gene_count(shape))), kinds, opp, mult
+        return rng.standard_normal((n, gene_count(shape))), rng.standard_normal((hall, gene_count(shape))), kinds, opp, mult
     genomes, members, kinds, opp, mult = population(shape, "relu", n=n, hall=hall, seed=sum(shape))
     if not bias:
         genomes, members = _without_bias(shape, genomes), _without_bias(shape, members)
@@ -58,8 +58,8 @@ def _play_both(gpu, oracle, shape, kernel, pop, dtype=torch.float64, bias=True, 
     assert (mult < 0).any() and (mult > 0).any() and (kinds[0] == [0, 1, 2, 3, 3, 3]).all() and (kinds[-1] == 3).all()
     ev = Evaluator(shape, device=gpu, dtype=dtype, bias=bias, activation="relu")
     assert ev.resolved_kernel(kernel, traced=bool(kw)) == kernel
-    res, trace = ev.evaluate(_dev_genomes(genomes, gpu, dtype), *[torch.tensor(a, device=gpu) for a in (kinds, opp, mult)],
-                             opponents=_dev_genomes(members, gpu, dtype), kernel=kernel, **kw)
+    res, trace = ev.evaluate(dev_genomes(genomes, gpu, dtype), *[torch.tensor(a, device=gpu) for a in (kinds, opp, mult)],
+                             opponents=dev_genomes(members, gpu, dtype), kernel=kernel, **kw)
     torch.cuda.synchronize()
     ref = oracle.eval_population(genomes, shape, kinds, opp, mult, opponents=members, bias=bias, base_seed=ev.seed,
                                  n_threads=8, activation="relu")
@@ -80,7 +80,7 @@ GENERAL = [([6, 64, 3], torch.float64, True), ([6, 200, 4], torch.float32, True)
            ([6, 130, 100, 2], torch.float64, True), ([6, 1, 2], torch.float64, True), ([6, 16, 3], torch.float64, False)]
 
 
-@pytest.mark.parametrize("shape,dtype,bias", GENERAL, ids=_ids)
+@pytest.mark.parametrize("shape,dtype,bias", GENERAL, ids=ids)
 def test_general_kernel_equals_oracle(gpu, oracle, shape, dtype, bias):
     """np.dot's summation order changes with the width (or_blas_dot's kinds and
     tails): 1 to 200 units, one and two hidden layers, f32 genes (the rounded
@@ -134,7 +134,7 @@ def test_general_kernel_traces_equal_oracle(gpu, oracle):
 
 
 # ------------------------------------------------------- 2 the hot kernels ----
-@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=_ids)
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=ids)
 def test_relu2_block_equals_oracle(gpu, oracle, dtype):
     shape = [6, 100, 72, 3]  # above 64 units in each hidden layer
     genomes, members, kinds, opp, mult = _population(shape)
@@ -145,7 +145,7 @@ def test_relu2_block_equals_oracle(gpu, oracle, dtype):
     assert shares[0] > 0 and shares[1] > 0, shares
 
 
-@pytest.mark.parametrize("shape,n,hall", [([6, 130, 100, 2], N, HALL), ([6, 512, 512, 3], 3, 2)], ids=_ids)
+@pytest.mark.parametrize("shape,n,hall", [([6, 130, 100, 2], N, HALL), ([6, 512, 512, 3], 3, 2)], ids=ids)
 def test_relu_wide_equals_oracle(gpu, oracle, shape, n, hall):
     genomes, members, kinds, opp, mult = _population(shape, n=n, hall=hall)
     _, res, _, ref = _play_both(gpu, oracle, shape, "relu_wide", (genomes, members, kinds, opp, mult))

@@ -9,24 +9,17 @@ whole games (tests/test_gpu_relu.py pins it to the reference's numpy loop).
 No transcendental is involved, so every comparison is exact (activations bit
 for bit, up to the sign of zero)."""
 import hashlib
-import importlib
-import random
 
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _dev_genomes, _gene_count
+from _gpu_support import FIELDS, dev_genomes, dropin_config, dropin_fitness, gene_count, ids, refused, same
 from test_gpu_wide import _schedule
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 DTYPES = [torch.float64, torch.float32]
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, list) else str(v).replace("torch.", "")
 
 
 def _relu_ev(shape, gpu, **kw):
@@ -39,18 +32,12 @@ def _bits(a):
     return (np.asarray(a, dtype=np.float64) + 0.0).view(np.int64)
 
 
-def _same(a, b, n=None):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert torch.equal(x[:n], y[:n]), name
-
-
 def _f32(a):
     return np.asarray(a).astype(np.float32).astype(np.float64)
 
 
 # ------------------------------------------------- 1 the reference's numbers ----
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
 @pytest.mark.parametrize("key", ["6x100x130x2", "6x512x512x2"])
 def test_decide_equals_reference(gpu, golden, key, dtype):
     """NeuralNetwork.run of the reference with ReLU on the game's k/320 grid:
@@ -66,13 +53,13 @@ def test_decide_equals_reference(gpu, golden, key, dtype):
         rows = []
         for seed, dist, sha in zip(g[f"{key}__seed"], g[f"{key}__dist"], g[f"{key}__genes_sha256"]):
             rng = np.random.default_rng(int(seed))
-            row = _f32(rng.random(_gene_count(shape)) if str(dist) == "init" else rng.standard_normal(_gene_count(shape)))
+            row = _f32(rng.random(gene_count(shape)) if str(dist) == "init" else rng.standard_normal(gene_count(shape)))
             assert hashlib.sha256(row.tobytes()).hexdigest() == str(sha)
             rows.append(row)
         genes = np.array(rows)
     np.testing.assert_array_equal(_f32(genes), genes)
     ev = _relu_ev(shape, gpu, dtype=dtype)
-    index, act = ev.relu_wide_decide(_dev_genomes(genes, gpu, dtype), torch.tensor(g[f"{key}__k"].astype(np.int32), device=gpu),
+    index, act = ev.relu_wide_decide(dev_genomes(genes, gpu, dtype), torch.tensor(g[f"{key}__k"].astype(np.int32), device=gpu),
                                      genome_index=torch.tensor(g[f"{key}__gidx"].astype(np.int32), device=gpu))
     torch.cuda.synchronize()
     np.testing.assert_array_equal(index.cpu().numpy(), g[f"{key}__idx"])
@@ -87,14 +74,14 @@ _PASS_NETS = [([6, 100, 130, 4], torch.float32, True), ([6, 40, 24, 2], torch.fl
 # (1e150 is not an f32 value: the f64-storage networks carry that case)
 @pytest.mark.parametrize("shape,dtype,bias,genes", [
     (s, d, b, g) for s, d, b in _PASS_NETS for g in ("n1", "init", "n1e150", "zero") if g != "n1e150" or d == torch.float64],
-    ids=_ids)
+    ids=ids)
 def test_decide_equals_f64_forward(gpu, shape, dtype, bias, genes):
     """16 networks x 128 inputs: index and activations equal pg_forward's f64
     path exactly -- N(0,1) and U[0,1) genes, N(0,1) * 1e150 (f64 storage only:
     inf and NaN territory, np.argmax takes the first NaN) and the all-zero
     genome (index 0, every activation 0)."""
     rng = np.random.default_rng(sum(shape) + len(genes) + int(bias))
-    G = _gene_count(shape, bias)
+    G = gene_count(shape, bias)
     w = {"n1": lambda: rng.standard_normal((16, G)), "init": lambda: rng.random((16, G)),
          "n1e150": lambda: rng.standard_normal((16, G)) * 1e150, "zero": lambda: np.zeros((16, G))}[genes]()
     if dtype == torch.float32:
@@ -102,9 +89,9 @@ def test_decide_equals_f64_forward(gpu, shape, dtype, bias, genes):
     k = rng.integers(0, 321, size=(16 * 128, 6)).astype(np.int32)
     gidx = np.repeat(np.arange(16), 128).astype(np.int32)
     ev = _relu_ev(shape, gpu, dtype=dtype, bias=bias)
-    gt, kt, it = _dev_genomes(w, gpu, dtype), torch.tensor(k, device=gpu), torch.tensor(gidx, device=gpu)
+    gt, kt, it = dev_genomes(w, gpu, dtype), torch.tensor(k, device=gpu), torch.tensor(gidx, device=gpu)
     index, act = ev.relu_wide_decide(gt, kt, genome_index=it)
-    ref_idx, ref_act = ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64")
+    ref_idx, ref_act = ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64")
     torch.cuda.synchronize()
     index, act, ref_idx, ref_act = (t.cpu().numpy() for t in (index, act, ref_idx, ref_act))
     np.testing.assert_array_equal(index, ref_idx)
@@ -133,7 +120,7 @@ def _traced_case(n_games):
     which the test asserts again from the general kernel's trace alone."""
     shape = [6, 96, 80, 3]
     rng = np.random.default_rng(300 + n_games)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 13, 4
     genomes, opponents = rng.standard_normal((n, G)), rng.standard_normal((H, G))
     kinds, opp, mult = _schedule(rng, n, n_games, H, nn_frac=0.8)
@@ -156,9 +143,9 @@ def test_relu_wide_equals_general_with_traces(gpu, n_games):
     n = len(genomes)
     ev = _relu_ev(shape, gpu, n_games=n_games)
     cap = 3000
-    args = (_dev_genomes(genomes, gpu), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
+    args = (dev_genomes(genomes, gpu), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
             torch.tensor(mult, device=gpu))
-    kw = dict(opponents=_dev_genomes(opponents, gpu), trace_games=n * n_games, trace_cap=cap)
+    kw = dict(opponents=dev_genomes(opponents, gpu), trace_games=n * n_games, trace_cap=cap)
     rg, tg = ev.evaluate(*args, kernel="general", **kw)
     rw, tw = ev.evaluate(*args, kernel="relu_wide", **kw)
     torch.cuda.synchronize()
@@ -166,7 +153,7 @@ def test_relu_wide_equals_general_with_traces(gpu, n_games):
     variety = _variety(tg, rg.frames.clamp(max=cap))
     print(f"n_games {n_games}: {variety:.3f} of {n * n_games} traced games move the right paddle both ways")
     assert variety >= 0.25
-    _same(rw, rg)
+    same(rw, rg)
     assert torch.equal(tw, tg) and int(tw.any())
     c = rw.counters.cpu().numpy()
     assert torch.equal(rw.counters[1:4], rg.counters[1:4])
@@ -182,21 +169,21 @@ def test_relu_wide_equals_general_with_traces(gpu, n_games):
     ([6, 100, 130, 4], True, torch.float32, "certified"),
     ([6, 65, 64, 3], True, torch.float32, "certified"),   # the first shape past k_relu2
     ([6, 64, 64, 3], True, torch.float64, "f64"),
-], ids=_ids)
+], ids=ids)
 def test_relu_wide_layouts_equal_general(gpu, shape, bias, dtype, precision):
     rng = np.random.default_rng(sum(shape) + 7)
-    G = _gene_count(shape, bias)
+    G = gene_count(shape, bias)
     n, H = 21, 5
     genomes, opponents = rng.standard_normal((n, G)) * 2.0, rng.standard_normal((H, G)) * 2.0
     genomes[::3] = rng.random((len(genomes[::3]), G))
     kinds, opp, mult = _schedule(rng, n, 6, H)
     ev = _relu_ev(shape, gpu, bias=bias, dtype=dtype, precision=precision, timeout_thresh=119, win_score=1)
-    args = (_dev_genomes(genomes, gpu, dtype), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
+    args = (dev_genomes(genomes, gpu, dtype), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
             torch.tensor(mult, device=gpu))
-    rw, _ = ev.evaluate(*args, opponents=_dev_genomes(opponents, gpu, dtype), kernel="relu_wide")
-    rg, _ = ev.evaluate(*args, opponents=_dev_genomes(opponents, gpu, dtype), kernel="general")
+    rw, _ = ev.evaluate(*args, opponents=dev_genomes(opponents, gpu, dtype), kernel="relu_wide")
+    rg, _ = ev.evaluate(*args, opponents=dev_genomes(opponents, gpu, dtype), kernel="general")
     torch.cuda.synchronize()
-    _same(rw, rg)
+    same(rw, rg)
     c = rw.counters.cpu().numpy()
     assert c[0] + c[8] == int(rw.frames.sum()) and c[3] == n * 6 and c[1] == int(rg.counters[1])
     assert c[2] == 0 and c[4] == 0 and c[7] > 0
@@ -209,7 +196,7 @@ def test_relu_wide_selfplay_default_limits(gpu):
     and permutation-equivariant (a genome's result does not depend on which
     workgroup or slot evaluated it)."""
     shape = [6, 96, 80, 3]
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 64, 16
     gen = torch.Generator(device=gpu).manual_seed(11)
     genomes = torch.randn((n, G), generator=gen, dtype=torch.float32, device=gpu)
@@ -223,7 +210,7 @@ def test_relu_wide_selfplay_default_limits(gpu):
     r2, _ = ev.evaluate(genomes[perm].contiguous(), kind[perm].contiguous(), opp[perm].contiguous(),
                         mult[perm].contiguous(), opponents=opponents)
     torch.cuda.synchronize()
-    _same(r1, rg)
+    same(r1, rg)
     for name in FIELDS:
         assert torch.equal(getattr(r2, name), getattr(r1, name)[perm]), name
     c = r1.counters.cpu().numpy()
@@ -235,25 +222,24 @@ def test_relu_wide_selfplay_default_limits(gpu):
 def test_relu_wide_config5_shape_equals_general(gpu):
     shape = [6, 512, 512, 3]
     rng = np.random.default_rng(512)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     n, H = 3, 2
     genomes, opponents = _f32(rng.standard_normal((n, G)) * 3.0), _f32(rng.standard_normal((H, G)) * 3.0)
     kinds = np.array([[0, 1, 2, 3, 3, 3], [3, 3, 3, 3, 3, 3], [3, 0, 3, 1, 3, 2]], np.int32)
     opp = rng.integers(0, H, size=(n, 6)).astype(np.int32)
     mult = np.ones((n, 6))
     ev = _relu_ev(shape, gpu, dtype=torch.float32, timeout_thresh=119, win_score=1)
-    args = (_dev_genomes(genomes, gpu, torch.float32), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
+    args = (dev_genomes(genomes, gpu, torch.float32), torch.tensor(kinds, device=gpu), torch.tensor(opp, device=gpu),
             torch.tensor(mult, device=gpu))
-    rw, _ = ev.evaluate(*args, opponents=_dev_genomes(opponents, gpu, torch.float32), kernel="relu_wide")
-    rg, _ = ev.evaluate(*args, opponents=_dev_genomes(opponents, gpu, torch.float32), kernel="general")
+    rw, _ = ev.evaluate(*args, opponents=dev_genomes(opponents, gpu, torch.float32), kernel="relu_wide")
+    rg, _ = ev.evaluate(*args, opponents=dev_genomes(opponents, gpu, torch.float32), kernel="general")
     torch.cuda.synchronize()
-    _same(rw, rg)
+    same(rw, rg)
     assert int(rw.counters[3]) == n * 6 and int(rw.counters[1]) == int(rg.counters[1]) and int(rw.counters[7]) > 0
 
 
 # ------------------------------------------------------------ 7 refusals ----
 def test_unsupported_combinations_are_refused(gpu):
-    from pong_amd import _lib
     from pong_amd.device import Evaluator
     shape = [6, 96, 80, 3]
     z = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
@@ -262,11 +248,6 @@ def test_unsupported_combinations_are_refused(gpu):
 
     def genomes(ev):
         return torch.zeros((4, ev.genes), dtype=torch.float64, device=gpu)
-
-    def refused(fn, word):
-        with pytest.raises(_lib.PongGAError) as e:
-            fn()
-        assert e.value.code == _lib.PG_ERR_UNSUPPORTED and word in str(e.value), str(e.value)
 
     ev = _relu_ev(shape, gpu)
     g = genomes(ev)
@@ -319,45 +300,20 @@ def test_device_ga_relu_wide_generations_and_checkpoint(gpu, tmp_path):
     assert torch.equal(ga.population_full(), ga2.population_full()) and torch.equal(ga.fitness, ga2.fitness)
 
 
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.fixture
 def relu_wide_dropin():
     """config.ACTIVATION = "relu" and config.KERNEL = "relu_wide" as a user sets
     them: numpy_nn initialises its activation_function from the knob when it is
     imported; the kernel knob is read at each call."""
-    import config
-    import numpy_nn
-    saved = (config.ACTIVATION, config.KERNEL)
-    config.ACTIVATION, config.KERNEL = "relu", "relu_wide"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="relu", kernel="relu_wide"):
+        import config
         yield config
-    finally:
-        config.ACTIVATION, config.KERNEL = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_equals_general(gpu, relu_wide_dropin):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on a [6,72,40,2] ReLU network
     with config.KERNEL = "relu_wide" against the same call with KERNEL =
     "general": the same hall, the same random seed, the same fitness."""
-    import ga
     import main
     import numpy_nn
     import utils
@@ -365,25 +321,20 @@ def test_dropin_evaluate_equals_general(gpu, relu_wide_dropin):
     assert numpy_nn.activation() == "relu"
     shape = [6, 72, 40, 2]
     rng = np.random.default_rng(78)
-    G = _gene_count(shape)
+    G = gene_count(shape)
     saved = (utils.NETWORK_SHAPE, main.hall_of_fame)
     try:
         utils.NETWORK_SHAPE = shape
         hall = rng.standard_normal((4, G))
         inds = [list(g) for g in rng.standard_normal((24, G))]
 
-        def fitness():  # (pick_hall_of_famer shuffles the hall in place: a fresh one, in the same order, per run)
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
-
         ev = main._evaluator()
         assert ev.activation == "relu" and list(ev.nodes) == shape and ev.kernel == "relu_wide"
-        got = fitness()
+        got = dropin_fitness(hall, inds)
         config.KERNEL = "general"
         ev_g = main._evaluator()
         assert ev_g is not ev and ev_g.kernel == "general"
-        want = fitness()
+        want = dropin_fitness(hall, inds)
         assert got == want and len(set(got)) >= 3
     finally:
         utils.NETWORK_SHAPE, main.hall_of_fame = saved

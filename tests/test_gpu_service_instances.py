@@ -20,7 +20,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import _assert_same, _dev_genomes, _gene_count
+from _gpu_support import assert_same, dev_genomes, gene_count
 
 pytestmark = pytest.mark.gpu
 
@@ -111,7 +111,7 @@ def _special_rows(rows, rng):
 
 def _population(H, O, bias, dtype):
     rng = np.random.default_rng([H, O, int(bias), dtype == "f32", 61])
-    G = _gene_count([6, H, O], bias)
+    G = gene_count([6, H, O], bias)
     quarters = np.array_split(np.arange(N), 4)
     genomes = np.empty((N, G))
     genomes[quarters[0]] = rng.standard_normal((len(quarters[0]), G))
@@ -147,13 +147,13 @@ def _cell(gpu, oracle, H, O, bias, dtype):
     assert (ref["status"] == 0).all() and np.isfinite(ref["fitness"]).all()
     ones = {r: oracle.eval_population(genomes[[r]], shape, kinds[[r]], opp[[r]], mult[[r]], opponents=opponents,
                                       bias=bias, n_threads=8) for r in (0, 2)}
-    gt, ot = _dev_genomes(genomes, gpu, dt), _dev_genomes(opponents, gpu, dt)
+    gt, ot = dev_genomes(genomes, gpu, dt), dev_genomes(opponents, gpu, dt)
     sched = _sched(gpu, kinds, opp, mult)
     cap = int(ref["frames"].max()) + 1
     gen = Evaluator(shape, bias=bias, dtype=dt, device=gpu, kernel="general", precision="f64")
     res, trace = gen.evaluate(gt, *sched, opponents=ot, trace_games=N * GAMES, trace_cap=cap)
     torch.cuda.synchronize()
-    _assert_same(res, ref)
+    assert_same(res, ref)
     assert int(trace.any())
     _CELL.clear()
     _CELL.update(key=key, genomes=genomes, kinds=kinds, opp=opp, mult=mult, ref=ref, ones=ones, gt=gt, ot=ot,
@@ -196,7 +196,7 @@ def test_service_games_every_instance(gpu, oracle, H, O, bias, dtype, L):
     print(f"[6,{H},{O}] bias={int(bias)} {dtype} L{L}U{U}: numpy-order f64 [2]={n[2]} certificate failures [4]={n[4]} "
           f"certified f64 [5]={n[5]} in-wave [6]={n[6]} rally frames [8]={n[8]} serve-delay frames [12]={n[12]} "
           f"of {int(ref['frames'].sum())} frames, longest game {c['cap'] - 1}")
-    _assert_same(res, ref)
+    assert_same(res, ref)
     assert n[3] == total and n[0] + n[8] + n[12] == ref["frames"].sum(), n
     # the all-zero network's outputs are exactly equal on every frame: no f32 rule and no certified
     # f64 rule tells them apart, so every instance reaches the numpy-order forward
@@ -205,7 +205,7 @@ def test_service_games_every_instance(gpu, oracle, H, O, bias, dtype, L):
     res_t, trace = ev.evaluate(c["gt"], *c["sched"], opponents=c["ot"], trace_games=total, trace_cap=c["cap"])
     torch.cuda.synchronize()
     t = res_t.counters.cpu().numpy().astype(np.int64)
-    _assert_same(res_t, ref)
+    assert_same(res_t, ref)
     assert t[8] == 0 and t[12] == 0 and t[0] == ref["frames"].sum() and t[3] == total, t
     assert torch.equal(trace, c["trace"])
     # one genome: a single, mostly empty block
@@ -213,7 +213,7 @@ def test_service_games_every_instance(gpu, oracle, H, O, bias, dtype, L):
         one, _ = ev.evaluate(c["gt"][r:r + 1].contiguous(), *_sched(gpu, c["kinds"], c["opp"], c["mult"], [r]),
                              opponents=c["ot"])
         torch.cuda.synchronize()
-        _assert_same(one, c["ones"][r])
+        assert_same(one, c["ones"][r])
         assert int(one.counters[3]) == GAMES
 
 
@@ -227,7 +227,7 @@ def test_service_refuses_what_no_instance_holds(gpu, H, L, dtype):
     assert H > 256 or _service_units(L, H) == 0
     genomes, opponents, kinds, opp, mult = _population(H, 3, True, dtype)
     ev = Evaluator([6, H, 3], dtype=DTYPES[dtype], device=gpu, kernel="split", group_lanes=L)
-    gt, ot = _dev_genomes(genomes, gpu, DTYPES[dtype]), _dev_genomes(opponents, gpu, DTYPES[dtype])
+    gt, ot = dev_genomes(genomes, gpu, DTYPES[dtype]), dev_genomes(opponents, gpu, DTYPES[dtype])
     sched = _sched(gpu, kinds, opp, mult)
     # marked result arrays: the refused call must leave them as they are
 
@@ -260,7 +260,7 @@ def _run_decide(ev, gpu, gt, k, gidx):
     it = torch.tensor(gidx.astype(np.int32), device=gpu)
     index, stage = ev.decide(gt, kt, genome_index=it)
     # the features as the kernels make them from the doubled centroids: (k / 2) / 160 (utils.inference)
-    want, _ = ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_act=False)
+    want, _ = ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_act=False)
     torch.cuda.synchronize()
     return index.cpu().numpy(), stage.cpu().numpy(), want.cpu().numpy()
 
@@ -274,7 +274,7 @@ def test_decide_every_instance(gpu, oracle, H, O, dtype):
     from pong_amd.device import Evaluator
     shape = [6, H, O]
     rng = np.random.default_rng([H, O, dtype == "f32", 67])
-    G = _gene_count(shape)
+    G = gene_count(shape)
     nets = np.concatenate([rng.random((8, G))] + [rng.standard_normal((8, G)) * s for s in (1.0, 3.0, 9.0, 30.0)])
     _special_rows(nets, rng)
     nets = _as_stored(nets, dtype)
@@ -283,7 +283,7 @@ def test_decide_every_instance(gpu, oracle, H, O, dtype):
     k[0::per], k[1::per] = 0, 320
     gidx = np.repeat(np.arange(n_nets), per)
     ev = Evaluator(shape, dtype=DTYPES[dtype], device=gpu)
-    gt = _dev_genomes(nets, gpu, DTYPES[dtype])
+    gt = dev_genomes(nets, gpu, DTYPES[dtype])
     index, stage, want = _run_decide(ev, gpu, gt, k, gidx)
     hist = np.bincount(stage, minlength=5)
     print(f"{shape} {dtype} L{_decide_layout(H)[0]}U{_decide_layout(H)[1]}: stages 0..4 {hist.tolist()}, "
@@ -314,7 +314,7 @@ def _near_tie_nets(H, O, rng):
     N(0,1) genes (outputs far below saturation), 4..7 with output biases of
     30 or 34 (the plateau regime, 22.2 <= z < 53 ln 2).  `step` is the relative
     change of the second row's largest weight; 0 = an exact copy."""
-    G, w2, row = _gene_count([6, H, O]), H * 7, H + 1
+    G, w2, row = gene_count([6, H, O]), H * 7, H + 1
     nets = rng.standard_normal((8, G))
     cases = [(0.0, None), (2.0 ** -22, None), (2.0 ** -16, None), (2.0 ** -22, None),
              (0.0, 30.0), (2.0 ** -22, 30.0), (None, 30.0), (2.0 ** -12, 34.0)]
@@ -386,7 +386,7 @@ def test_decide_near_ties_every_instance(gpu, oracle, host_sigmoid, H, O, dtype)
     k = rng.integers(0, 321, size=(len(nets) * per, 6))
     gidx = np.repeat(np.arange(len(nets)), per)
     ev = Evaluator(shape, dtype=DTYPES[dtype], device=gpu)
-    index, stage, want = _run_decide(ev, gpu, _dev_genomes(nets, gpu, DTYPES[dtype]), k, gidx)
+    index, stage, want = _run_decide(ev, gpu, dev_genomes(nets, gpu, DTYPES[dtype]), k, gidx)
     print(f"{shape} {dtype} L{_decide_layout(H)[0]}U{_decide_layout(H)[1]}: stages 0..4 per near-tie network "
           f"{[np.bincount(stage[gidx == i], minlength=5).tolist() for i in range(len(nets))]}")
     np.testing.assert_array_equal(index, want)
@@ -417,7 +417,7 @@ def test_prep_in_two_calls_off_the_bench_layout(gpu, L, dtype):
     genomes, opponents, kinds, opp, mult = _population(H, O, True, dtype)
     dt = DTYPES[dtype]
     ev = Evaluator([6, H, O], dtype=dt, device=gpu, kernel="split", group_lanes=L)
-    gt, ot = _dev_genomes(genomes, gpu, dt), _dev_genomes(opponents, gpu, dt)
+    gt, ot = dev_genomes(genomes, gpu, dt), dev_genomes(opponents, gpu, dt)
     sched = _sched(gpu, kinds, opp, mult)
     rng = np.random.default_rng([L, 71])
     rows = torch.tensor(rng.permutation(N).astype(np.int32), device=gpu)

@@ -6,24 +6,17 @@ Checkers: pg_forward in f64 (numpy's order, the correctly rounded sigmoid) for
 single decisions, numpy's own NeuralNetwork.run restated with np.dot where the
 host's pow decides the case as numpy's does, the general kernel for whole
 games, and the C oracle (which plays any sigmoid NETWORK_SHAPE)."""
-import importlib
-import random
 
 import numpy as np
 import pytest
 import torch
 
 import _sig2_model as M
-from test_gpu_parity import _assert_same, _dev_genomes, _run_both, _schedule
+from _gpu_support import assert_same, dev_genomes, dropin_config, dropin_fitness, ids, refused, run_both, same, schedule
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("fitness", "rewards", "scores", "frames", "total_frames", "status")
 DTYPES = [torch.float64, torch.float32]
-
-
-def _ids(v):
-    return "x".join(map(str, v)) if isinstance(v, list) else str(v).replace("torch.", "")
 
 
 def _ev(shape, gpu, **kw):
@@ -33,18 +26,18 @@ def _ev(shape, gpu, **kw):
 
 def _decide_both(ev, gpu, genomes, k, gidx):
     """sig2_decide and the f64 pg_forward on the same passes (genomes as ev's dtype holds them)."""
-    gt, kt = _dev_genomes(genomes, gpu, ev.dtype), torch.tensor(k.astype(np.int32), device=gpu)
+    gt, kt = dev_genomes(genomes, gpu, ev.dtype), torch.tensor(k.astype(np.int32), device=gpu)
     it = torch.tensor(gidx.astype(np.int32), device=gpu)
     index, stage, z32, bound = ev.sig2_decide(gt, kt, genome_index=it)
-    ref_idx, _ = ev.forward(gt, _dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_layers=True)
+    ref_idx, _ = ev.forward(gt, dev_genomes((k / 2) / 160, gpu), genome_index=it, precision="f64", want_layers=True)
     z64 = ev.last_layers[0][:, -ev.nodes[-1]:]
     torch.cuda.synchronize()
     return tuple(t.cpu().numpy() for t in (index, stage, z32, bound, ref_idx, z64))
 
 
 # ------------------------------------------------------- 1 random passes ----
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
-@pytest.mark.parametrize("shape", M.SHAPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+@pytest.mark.parametrize("shape", M.SHAPES, ids=ids)
 def test_decide_random_passes(gpu, shape, dtype):
     """64 networks x 512 inputs (U[0,1), N(0,1), N(0,3) and N(0,30) genes): the
     decision is the f64 forward's on every pass and |z32 - z64| stays within the
@@ -95,7 +88,7 @@ def _pad(b, O, fill=-5.0):
     return np.array(list(b) + [fill] * (O - len(b)))
 
 
-@pytest.mark.parametrize("shape", [[6, 16, 16, 3], [6, 17, 33, 4], [6, 20, 32, 4], [6, 5, 4, 2]], ids=_ids)
+@pytest.mark.parametrize("shape", [[6, 16, 16, 3], [6, 17, 33, 4], [6, 20, 32, 4], [6, 5, 4, 2]], ids=ids)
 def test_decide_built_cases(gpu, shape):
     _, H1, H2, O = shape
     rng = np.random.default_rng(5 + sum(shape))
@@ -152,12 +145,6 @@ def test_decide_built_cases(gpu, shape):
 
 
 # --------------------------------------------------------- 3 whole games ----
-def _same(a, b, n=None):
-    for name in FIELDS:
-        x, y = getattr(a, name), getattr(b, name)
-        assert torch.equal(x[:n], y[:n]), name
-
-
 def _hard_rows(shape, rng, n):
     """n genomes whose every forward fails the f32 certificate: two outputs on one plateau, an exact tie, the
     all-zero genome and every output below -709.8, in turn (f32 values throughout)."""
@@ -176,8 +163,8 @@ def _hard_rows(shape, rng, n):
     return np.array(rows).astype(np.float32).astype(np.float64)
 
 
-@pytest.mark.parametrize("dtype", DTYPES, ids=_ids)
-@pytest.mark.parametrize("shape", M.SHAPES, ids=_ids)
+@pytest.mark.parametrize("dtype", DTYPES, ids=ids)
+@pytest.mark.parametrize("shape", M.SHAPES, ids=ids)
 def test_sig2_kernel_equals_general(gpu, shape, dtype):
     """k_sig2's decisions are the f64 forward's: every output array, the
     per-frame traces of the first 64 games and the step / forward / game
@@ -186,7 +173,7 @@ def test_sig2_kernel_equals_general(gpu, shape, dtype):
     rng = np.random.default_rng(sum(shape) + 1)
     G = M.genes(shape)
     n, H = 256, 16
-    genomes, opponents = _dev_genomes(rng.standard_normal((n, G)), gpu, dtype), _dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
+    genomes, opponents = dev_genomes(rng.standard_normal((n, G)), gpu, dtype), dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
     kinds = np.tile(np.array([0, 1, 2, 3, 3, 3], np.int32), (n, 1))
     kinds[n // 2:] = 3
     opp = rng.integers(0, H, size=(n, 6)).astype(np.int32)
@@ -197,7 +184,7 @@ def test_sig2_kernel_equals_general(gpu, shape, dtype):
     hot, hot_tr = ev.evaluate(genomes, *sched, opponents=opponents, kernel="sig2", trace_games=64, trace_cap=2048)
     ref, ref_tr = ev.evaluate(genomes, *sched, opponents=opponents, kernel="general", trace_games=64, trace_cap=2048)
     torch.cuda.synchronize()
-    _same(hot, ref)
+    same(hot, ref)
     assert torch.equal(hot_tr, ref_tr) and int(hot_tr.any())
     ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all()
@@ -205,12 +192,12 @@ def test_sig2_kernel_equals_general(gpu, shape, dtype):
     print(f"{shape} {dtype}: stage-1 failures {ch[4] / ch[1]:.5f}, f64 {ch[2] / ch[1]:.5f} of {ch[1]} forwards")
     assert ch[2] <= ch[4] < ch[1]
     # genomes and opponents whose every forward fails stage 1
-    hard, hard_opp = _dev_genomes(_hard_rows(shape, rng, 64), gpu, dtype), _dev_genomes(_hard_rows(shape, rng, H), gpu, dtype)
+    hard, hard_opp = dev_genomes(_hard_rows(shape, rng, 64), gpu, dtype), dev_genomes(_hard_rows(shape, rng, H), gpu, dtype)
     hsched = [t[:64].contiguous() for t in sched]
     hot_h, tr_h = ev.evaluate(hard, *hsched, opponents=hard_opp, kernel="sig2", trace_games=64, trace_cap=2048)
     ref_h, rtr_h = ev.evaluate(hard, *hsched, opponents=hard_opp, kernel="general", trace_games=64, trace_cap=2048)
     torch.cuda.synchronize()
-    _same(hot_h, ref_h)
+    same(hot_h, ref_h)
     assert torch.equal(tr_h, rtr_h)
     chh = hot_h.counters.cpu().numpy()
     assert (chh[[0, 1, 3]] == ref_h.counters.cpu().numpy()[[0, 1, 3]]).all()
@@ -222,12 +209,12 @@ def test_sig2_kernel_equals_general(gpu, shape, dtype):
     ref2, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="general", rows=perm, n_active=act)
     whole, _ = ev.evaluate(genomes[perm.long()].contiguous(), *sched, opponents=opponents, kernel="sig2")
     torch.cuda.synchronize()
-    _same(hot2, ref2, 170)
-    _same(hot2, whole, 170)
+    same(hot2, ref2, 170)
+    same(hot2, whole, 170)
     assert int(hot2.counters[3]) == 170 * 6 == int(ref2.counters[3])
 
 
-@pytest.mark.parametrize("shape", [[6, 5, 4, 2], [6, 20, 32, 3], [6, 33, 17, 3]], ids=_ids)
+@pytest.mark.parametrize("shape", [[6, 5, 4, 2], [6, 20, 32, 3], [6, 33, 17, 3]], ids=ids)
 @pytest.mark.parametrize("dist", ["init", "n3"])
 def test_sig2_matches_oracle(gpu, oracle, shape, dist):
     """One shape per layout against the C oracle at default limits: n = 97, H = 13 (ragged)."""
@@ -236,17 +223,17 @@ def test_sig2_matches_oracle(gpu, oracle, shape, dist):
     n, H = 97, 13
     draw = (lambda s: rng.random(s)) if dist == "init" else (lambda s: rng.standard_normal(s) * 3.0)
     genomes, opponents = draw((n, G)), draw((H, G))
-    kinds, opp, mult = _schedule(rng, n, 6, H)
+    kinds, opp, mult = schedule(rng, n, 6, H)
     ev = _ev(shape, gpu, kernel="sig2")
-    res, ref = _run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
-    _assert_same(res, ref)
+    res, ref = run_both(ev, oracle, genomes, opponents, kinds, opp, mult, gpu)
+    assert_same(res, ref)
     c = res.counters.cpu().numpy()
     assert c[0] == int(ref["frames"].sum()) and c[8] == 0 and c[12] == 0 and c[2] <= c[4] <= c[1]
     print(f"{shape} {dist}: stage-1 failures {c[4] / c[1]:.5f}, f64 {c[2] / c[1]:.5f} of {c[1]} forwards")
 
 
 @pytest.mark.parametrize("shape,n,dtype", [([6, 16, 16, 3], 4096, torch.float64), ([6, 20, 32, 4], 1024, torch.float32),
-                                           ([6, 64, 64, 3], 1024, torch.float64)], ids=_ids)
+                                           ([6, 64, 64, 3], 1024, torch.float64)], ids=ids)
 def test_sig2_groups_play_several_games(gpu, shape, n, dtype):
     """More games than the launch has lane groups (2 blocks per CU of 32, 8 or 4
     groups), so every group takes further games from the queue and replaces its
@@ -257,7 +244,7 @@ def test_sig2_groups_play_several_games(gpu, shape, n, dtype):
     groups = 2 * torch.cuda.get_device_properties(gpu).multi_processor_count * (256 // (2 * LN))
     assert n * 6 > 1.4 * groups
     H = 64
-    genomes, opponents = _dev_genomes(rng.standard_normal((n, G)), gpu, dtype), _dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
+    genomes, opponents = dev_genomes(rng.standard_normal((n, G)), gpu, dtype), dev_genomes(rng.standard_normal((H, G)), gpu, dtype)
     kinds = np.tile(np.array([0, 1, 2, 3, 3, 3], np.int32), (n, 1))
     kinds[n // 2:] = 3
     sched = [torch.tensor(a, device=gpu) for a in (kinds, rng.integers(0, H, size=(n, 6)).astype(np.int32),
@@ -266,12 +253,12 @@ def test_sig2_groups_play_several_games(gpu, shape, n, dtype):
     hot, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="sig2")
     ref, _ = ev.evaluate(genomes, *sched, opponents=opponents, kernel="general")
     torch.cuda.synchronize()
-    _same(hot, ref)
+    same(hot, ref)
     ch, cr = hot.counters.cpu().numpy(), ref.counters.cpu().numpy()
     assert (ch[[0, 1, 3]] == cr[[0, 1, 3]]).all() and ch[3] == n * 6 and ch[2] <= ch[4] < ch[1]
 
 
-@pytest.mark.parametrize("shape", [[6, 2, 2, 2], [6, 17, 3, 3], [6, 33, 64, 4]], ids=_ids)
+@pytest.mark.parametrize("shape", [[6, 2, 2, 2], [6, 17, 3, 3], [6, 33, 64, 4]], ids=ids)
 def test_sig2_counter_flush(gpu, shape):
     """The shared game loop's flush of a family whose stages are 0..3: [2] the
     f64 forwards (stage 3) <= [4] the stage-1 failures (stage > 0) <= [1] the
@@ -280,8 +267,8 @@ def test_sig2_counter_flush(gpu, shape):
     the rows fail stage 1 at every forward."""
     rng = np.random.default_rng(sum(shape) + 3)
     G = M.genes(shape)
-    genomes = _dev_genomes(np.concatenate([rng.standard_normal((4, G)), _hard_rows(shape, rng, 4)]), gpu, torch.float64)
-    hall = _dev_genomes(np.concatenate([rng.standard_normal((2, G)), _hard_rows(shape, rng, 2)]), gpu, torch.float64)
+    genomes = dev_genomes(np.concatenate([rng.standard_normal((4, G)), _hard_rows(shape, rng, 4)]), gpu, torch.float64)
+    hall = dev_genomes(np.concatenate([rng.standard_normal((2, G)), _hard_rows(shape, rng, 2)]), gpu, torch.float64)
     sched = [torch.tensor(a, device=gpu) for a in (np.full((8, 2), 3, np.int32), rng.integers(0, 4, size=(8, 2)).astype(np.int32),
                                                    np.ones((8, 2)))]
     ev = _ev(shape, gpu, n_games=2, timeout_thresh=119, win_score=1)
@@ -293,7 +280,6 @@ def test_sig2_counter_flush(gpu, shape):
 
 # ------------------------------------------------------------ 4 refusals ----
 def test_unsupported_combinations_are_refused(gpu):
-    from pong_amd import _lib
     shape = [6, 16, 16, 3]
     z = torch.zeros((4, 6), dtype=torch.int32, device=gpu)
     m = torch.ones((4, 6), dtype=torch.float64, device=gpu)
@@ -301,11 +287,6 @@ def test_unsupported_combinations_are_refused(gpu):
 
     def genomes(ev):
         return torch.zeros((4, ev.genes), dtype=torch.float64, device=gpu)
-
-    def refused(fn, word):
-        with pytest.raises(_lib.PongGAError) as e:
-            fn()
-        assert e.value.code == _lib.PG_ERR_UNSUPPORTED and word in str(e.value), str(e.value)
 
     ev = _ev(shape, gpu)
     g = genomes(ev)
@@ -325,14 +306,14 @@ def test_unsupported_combinations_are_refused(gpu):
             "hard")
     # the supported neighbours of the refused calls still run; AUTO has not moved: it is the general kernel
     rng = np.random.default_rng(3)
-    gr = _dev_genomes(rng.standard_normal((4, ev.genes)) * 3.0, gpu)
+    gr = dev_genomes(rng.standard_normal((4, ev.genes)) * 3.0, gpu)
     got = {kernel: ev.evaluate(gr, z, z, m, kernel=kernel)[0] for kernel in ("sig2", "general", "auto")}
     torch.cuda.synchronize()
     c = {kernel: r.counters.cpu().numpy() for kernel, r in got.items()}
     assert c["sig2"][3] == c["general"][3] == 24
     assert (c["auto"] == c["general"]).all()
-    _same(got["sig2"], got["general"])
-    _same(got["auto"], got["general"])
+    same(got["sig2"], got["general"])
+    same(got["auto"], got["general"])
     index, stage, _, _ = ev.sig2_decide(g, k)  # all-zero genes: every output 0.5, index 0, decided in f64
     assert (index.cpu().numpy() == 0).all() and (stage.cpu().numpy() == 3).all()
 
@@ -364,43 +345,18 @@ def test_device_ga_sig2_generations_and_checkpoint(gpu, tmp_path):
     assert torch.equal(ga.population_full(), ga2.population_full()) and torch.equal(ga.fitness, ga2.fitness)
 
 
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.fixture
 def sig2_dropin():
     """config.KERNEL = "sig2" as a user sets it (the knob is read at each call; the activation is the default sigmoid)."""
-    import config
-    import numpy_nn
-    saved = (config.ACTIVATION, config.KERNEL)
-    config.ACTIVATION, config.KERNEL = "sigmoid", "sig2"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="sigmoid", kernel="sig2"):
+        import config
         yield config
-    finally:
-        config.ACTIVATION, config.KERNEL = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_equals_default(gpu, sig2_dropin):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on a [6,16,16,2] sigmoid network
     with config.KERNEL = "sig2" against the same call with the default KERNEL =
     "auto": the same hall, the same random seed, the same fitness."""
-    import ga
     import main
     import numpy_nn
     import utils
@@ -415,18 +371,13 @@ def test_dropin_evaluate_equals_default(gpu, sig2_dropin):
         hall = rng.standard_normal((4, G))
         inds = [list(g) for g in rng.standard_normal((24, G))]
 
-        def fitness():  # (pick_hall_of_famer shuffles the hall in place: a fresh one, in the same order, per run)
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
-
         ev = main._evaluator()
         assert ev.activation == "sigmoid" and list(ev.nodes) == shape and ev.kernel == "sig2"
-        got = fitness()
+        got = dropin_fitness(hall, inds)
         config.KERNEL = "auto"
         ev_d = main._evaluator()
         assert ev_d is not ev and ev_d.kernel == "auto"
-        want = fitness()
+        want = dropin_fitness(hall, inds)
         assert got == want and len(set(got)) >= 3
     finally:
         utils.NETWORK_SHAPE, main.hall_of_fame = saved

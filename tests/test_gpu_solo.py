@@ -8,16 +8,13 @@ status, and (against the base kernel) equality of all 16 counters.  The
 populations, shapes and limits are test_gpu_advance's: 192 noisy trackers and a
 hall of 24, rows below 96 playing kinds [0,1,2,3,3,3] and the rest all-NN.
 """
-import importlib
-import random
 
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_advance import (DEFAULT, F32_SHAPE, FAMILIES, FIELDS, SERVE, SHAPES, SHORT, _HoF, _Member, _genes, _ids,
-                              population, runs)
-from test_gpu_parity import _dev_genomes
+from _gpu_support import FIELDS, dev_genomes, dropin_config, dropin_fitness, ids
+from test_gpu_advance import DEFAULT, F32_SHAPE, FAMILIES, SERVE, SHAPES, SHORT, _genes, population, runs
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +52,7 @@ def _assert_solo_equals_base(ev, data, family, base, base_adv, general, what):
 CASES = [(f, s, torch.float64) for f in FAMILIES for s in SHAPES[f]] + [(f, F32_SHAPE[f], torch.float32) for f in FAMILIES]
 
 
-@pytest.mark.parametrize("family,shape,dtype", CASES, ids=_ids)
+@pytest.mark.parametrize("family,shape,dtype", CASES, ids=ids)
 def test_solo_equals_base(gpu, family, shape, dtype):
     ev, data, got = runs(gpu, family, shape, dtype)
     kinds = data["host"][2]
@@ -76,7 +73,7 @@ def _custom(gpu, family, shape, kinds, n_games=6, with_hall=True, n=None, hall=8
     genomes, members, _, opp, mult = population(shape, act, n, hall)
     ev = Evaluator(shape, device=gpu, activation=act, n_games=n_games)
     sched = [torch.tensor(np.ascontiguousarray(a[:, :n_games]), device=gpu) for a in (kinds, opp, mult)]
-    data = dict(genomes=_dev_genomes(genomes, gpu), opponents=_dev_genomes(members, gpu) if with_hall else None, sched=sched)
+    data = dict(genomes=dev_genomes(genomes, gpu), opponents=dev_genomes(members, gpu) if with_hall else None, sched=sched)
     return ev, data
 
 
@@ -112,7 +109,7 @@ def test_solo_one_game_launch(gpu, family, kind):
 
 # -------------------------------------------------------------- 3 reloads ----
 @pytest.mark.parametrize("family,shape,n", [("relu", [6, 2, 2], 4096), ("relu2", [6, 2, 2, 2], 4096),
-                                            ("sig2", [6, 33, 64, 4], 1024)], ids=_ids)
+                                            ("sig2", [6, 33, 64, 4], 1024)], ids=ids)
 def test_groups_reload_and_pass_from_pair_to_solo_games(gpu, family, shape, n):
     """More NN games than the launch has lane groups, so groups reload pair
     games and later pass on to solo games, each half on its own.  No counter
@@ -138,7 +135,7 @@ def test_groups_reload_and_pass_from_pair_to_solo_games(gpu, family, shape, n):
 
 
 # --------------------------------------------------------------- 4 limits ----
-@pytest.mark.parametrize("limits", [SHORT, SERVE], ids=_ids)
+@pytest.mark.parametrize("limits", [SHORT, SERVE], ids=ids)
 @pytest.mark.parametrize("family", list(FAMILIES))
 def test_solo_under_other_limits(gpu, family, limits):
     shape = SHAPES[family][0]
@@ -198,7 +195,7 @@ def test_traced_solo_launch(gpu, family):
 
 
 # ----------------------------------------------------------------- 7 AUTO ----
-@pytest.mark.parametrize("family,shape", [("relu", [6, 2, 2]), ("relu2", [6, 2, 2, 2])], ids=_ids)
+@pytest.mark.parametrize("family,shape", [("relu", [6, 2, 2]), ("relu2", [6, 2, 2, 2])], ids=ids)
 def test_auto_solo_in_the_relu_scopes(gpu, family, shape):
     ev, data, got = runs(gpu, family, shape)
     for mods in ("+solo", "+advance+solo"):
@@ -210,14 +207,14 @@ def test_auto_solo_in_the_relu_scopes(gpu, family, shape):
 
 
 @pytest.mark.parametrize("activation,shape", [("sigmoid", [6, 64, 3]), ("relu", [6, 4, 4, 4, 2]),
-                                              ("sigmoid", [6, 16, 16, 3])], ids=_ids)
+                                              ("sigmoid", [6, 16, 16, 3])], ids=ids)
 def test_auto_solo_changes_nothing_elsewhere(gpu, activation, shape):
     """Where AUTO resolves to SPLIT ([6,64,3] sigmoid) or GENERAL the bit changes nothing."""
     from pong_amd.device import Evaluator
     genomes, members, kinds, opp, mult = population(shape, activation, n=48, hall=8)
     ev = Evaluator(shape, device=gpu, activation=activation)
-    args = [_dev_genomes(genomes, gpu)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
-    got = {k: ev.evaluate(*args, opponents=_dev_genomes(members, gpu), kernel=k)[0]
+    args = [dev_genomes(genomes, gpu)] + [torch.tensor(a, device=gpu) for a in (kinds, opp, mult)]
+    got = {k: ev.evaluate(*args, opponents=dev_genomes(members, gpu), kernel=k)[0]
            for k in ("auto+solo", "auto+advance+solo", "auto")}
     torch.cuda.synchronize()
     _equal(got["auto+solo"], got["auto"])
@@ -250,23 +247,15 @@ def test_device_ga_auto_solo_generations(gpu):
 @pytest.fixture
 def relu_dropin():
     """config.ACTIVATION = "relu" as a user sets it; the test sets config.KERNEL."""
-    import config
-    import numpy_nn
-    saved = (config.ACTIVATION, config.KERNEL)
-    config.ACTIVATION = "relu"
-    importlib.reload(numpy_nn)
-    try:
+    with dropin_config(activation="relu"):
+        import config
         yield config
-    finally:
-        config.ACTIVATION, config.KERNEL = saved
-        importlib.reload(numpy_nn)
 
 
 def test_dropin_evaluate_equals_auto(gpu, relu_dropin):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on a [6,16,3] ReLU network with
     config.KERNEL = "auto+solo" and "auto+advance+solo" against "auto": the same
     hall, the same random seed, the same fitness."""
-    import ga
     import main
     import utils
     config = relu_dropin
@@ -283,9 +272,7 @@ def test_dropin_evaluate_equals_auto(gpu, relu_dropin):
             config.KERNEL = kernel
             ev = main._evaluator()
             assert ev.activation == "relu" and list(ev.nodes) == shape and ev.kernel == kernel
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
+            return dropin_fitness(hall, inds)
 
         want = fitness("auto")
         assert len(set(want)) >= 3

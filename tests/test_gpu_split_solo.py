@@ -8,14 +8,13 @@ the base instances and the CPU oracle.
 status and on all 16 counters.  Every case first asks pg_eval_resolve
 (Evaluator.resolved_kernel) which instance it is about to run.
 """
-import random
 
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_advance import FIELDS, SERVE, SHORT, _HoF, _ids, _Member, population
-from test_gpu_parity import _assert_same, _dev_genomes, _gene_count
+from _gpu_support import FIELDS, assert_same, dev_genomes, dropin_fitness, gene_count, ids
+from test_gpu_advance import SERVE, SHORT, population
 from test_gpu_service_instances import DTYPES, _as_stored, _special_rows
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +41,7 @@ def _varied(shape, bias, dtype, n=N, hall=HALL, seed=0):
     """(genomes, hall, kinds, opp, mult): N(0,1), N(0,9), U[0,1) and N(0,81) genes by
     quarters, rows 0..4 the all-zero, over-cap, NaN and infinite networks."""
     rng = np.random.default_rng([*shape, int(bias), dtype == "f32", seed, 73])
-    G = _gene_count(shape, bias)
+    G = gene_count(shape, bias)
     genomes = np.empty((n, G))
     for q, rows in enumerate(np.array_split(np.arange(n), 4)):
         genomes[rows] = rng.random((len(rows), G)) if q == 2 else rng.standard_normal((len(rows), G)) * (1.0, 3.0, 0, 9.0)[q]
@@ -55,7 +54,7 @@ def _varied(shape, bias, dtype, n=N, hall=HALL, seed=0):
 
 def _on_device(gpu, host, dt=torch.float64, with_hall=True, n_games=6):
     genomes, members, kinds, opp, mult = host
-    return dict(genomes=_dev_genomes(genomes, gpu, dt), opponents=_dev_genomes(members, gpu, dt) if with_hall else None,
+    return dict(genomes=dev_genomes(genomes, gpu, dt), opponents=dev_genomes(members, gpu, dt) if with_hall else None,
                 sched=[torch.tensor(np.ascontiguousarray(a[:, :n_games]), device=gpu) for a in (kinds, opp, mult)])
 
 
@@ -89,7 +88,7 @@ def test_every_routed_instance(gpu, oracle, H, O, dtype, bias):
     ev = Evaluator(shape, bias=bias, dtype=DTYPES[dtype], device=gpu)
     base, solo = _solo_equals_base(ev, _on_device(gpu, host, DTYPES[dtype]), f"{shape} {dtype} bias={bias}")
     ref = oracle.eval_population(genomes, shape, kinds, opp, mult, opponents=members, bias=bias, n_threads=8)
-    _assert_same(solo, ref)
+    assert_same(solo, ref)
     c = solo.counters.cpu().numpy()
     assert c[3] == N * 6 and c[0] + c[8] + c[12] == ref["frames"].sum() and c[12] > 0
     assert c[4] > 0 and c[2] > 0  # (the all-zero network reaches the numpy-order forward on every visible frame)
@@ -102,7 +101,7 @@ def test_cascade_under_sixteen_requesters(gpu):
     serve_inline meets up to 16 requesting half-groups of a wave."""
     from pong_amd.device import Evaluator
     rng = np.random.default_rng(11)
-    G = _gene_count(SHAPE, True)
+    G = gene_count(SHAPE, True)
     host = (rng.random((N, G)), rng.random((HALL, G)), _mixed_kinds(N), rng.integers(0, HALL, size=(N, 6)).astype(np.int32),
             np.ones((N, 6)))
     ev = Evaluator(SHAPE, device=gpu)
@@ -164,7 +163,7 @@ def test_groups_reload_and_pass_from_pair_to_solo_games(gpu):
 
 
 # ------------------------------------------- 5 limits, n_active, genome_rows ----
-@pytest.mark.parametrize("limits", [SHORT, SERVE], ids=_ids)
+@pytest.mark.parametrize("limits", [SHORT, SERVE], ids=ids)
 def test_under_other_limits(gpu, limits):
     from pong_amd.device import Evaluator
     host = population(SHAPE, "sigmoid")
@@ -270,11 +269,10 @@ def test_dropin_evaluate_equals_auto(gpu):
     """ga.toolbox.map(ga.toolbox.evaluate, ...) on the [6,64,3] sigmoid network with
     config.KERNEL = "auto+solo" against "auto": the same hall, the same random seed, the same fitness."""
     import config
-    import ga
     import main
     import utils
     rng = np.random.default_rng(81)
-    G = _gene_count(SHAPE, True)
+    G = gene_count(SHAPE, True)
     saved = (utils.NETWORK_SHAPE, main.hall_of_fame, config.KERNEL)
     try:
         utils.NETWORK_SHAPE = SHAPE
@@ -286,9 +284,7 @@ def test_dropin_evaluate_equals_auto(gpu):
             ev = main._evaluator()
             assert list(ev.nodes) == SHAPE and ev.kernel == kernel
             assert ev.resolved_kernel() == ("split+solo" if "solo" in kernel else "split")
-            main.hall_of_fame = _HoF([_Member(list(g), f) for g, f in zip(hall, (0.7, -0.3, 0.1, 0.0))])
-            random.seed(5)
-            return [fit[0] for fit in ga.toolbox.map(ga.toolbox.evaluate, inds)]
+            return dropin_fitness(hall, inds)
 
         want = fitness("auto")
         assert len(set(want)) >= 3

@@ -17,6 +17,8 @@ import random
 import numpy as np
 import pytest
 
+from _gpu_support import HoF, Member  # (the hall the reference's evaluate() reads: no GPU in it)
+
 KEYS = ["6x2x2", "6x64x2", "6x64x3", "6x8x8x3", "6x4x2_nobias"]
 
 
@@ -62,31 +64,14 @@ def test_episode_traces_match_reference(oracle, golden, name):
         assert ep["right_actions"][0] == 0 and ep["left_actions"][0] == 0  # BLANK_ACTION first
 
 
-class _Fit:
-    def __init__(self, v):
-        self.values = (v,)
-        self.valid = True
-
-
-class _Member(list):
-    def __init__(self, genes, fit):
-        super().__init__(genes)
-        self.fitness = _Fit(fit)
-
-
-class _HoF:
-    def __init__(self, items):
-        self.items = items
-
-
 @pytest.mark.parametrize("name", ["evaluate.json", "evaluate_s3.json"])
 def test_evaluate_matches_reference(oracle, golden, name):
     import utils
     from pong_amd import schedule
     for case in golden(name):
         shape = case["shape"]
-        members = [_Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])]
-        hof = _HoF(members)
+        members = [Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])]
+        hof = HoF(members)
         random.seed(case["random_seed"])
         n = len(case["individuals"])
         kind, opp, mult, chosen = schedule.reference_schedule(n, 6, hof, utils.pick_hall_of_famer)

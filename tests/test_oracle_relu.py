@@ -23,11 +23,11 @@ import warnings
 import numpy as np
 import pytest
 
+from _gpu_support import HoF, Member
 from test_gpu_advance import population
 from test_gpu_modifier_instances import (CELLS, _cell_id, all_cells, cell_population, check_cell_population,
                                          oracle_result)
 from test_gpu_relu import _numpy_games
-from test_oracle_golden import _HoF, _Member
 
 
 def _bits(a):
@@ -84,7 +84,7 @@ def test_evaluate_matches_reference(oracle, golden):
     from pong_amd import schedule
     for case in golden("relu_evaluate.json"):
         assert case["activation"] == "relu"
-        hof = _HoF([_Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])])
+        hof = HoF([Member(g, f) for g, f in zip(case["hof_genes"], case["hof_fitness"])])
         random.seed(case["random_seed"])
         n = len(case["individuals"])
         kind, opp, mult, chosen = schedule.reference_schedule(n, 6, hof, utils.pick_hall_of_famer)
