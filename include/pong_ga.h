@@ -35,6 +35,7 @@
  * pg_relu2_block_decide          the same, as k_relu2_block decides it (two hidden layers of up to 128 units)
  * pg_relu_wide_decide            the same, as k_wide's ReLU instances decide it (wide ReLU networks)
  * pg_sig2_decide                 the same, as k_sig2 decides it (sigmoid networks with two hidden layers)
+ * pg_sig2_block_decide           the same, as k_sig2_block decides it (two hidden layers of up to 128 units)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
  *                                (the build's SoA Pong; the emulator is absent)
  * pg_ga_select_tournament        tools.selTournament (ga.py:94; DEAP)
@@ -115,7 +116,7 @@ typedef enum pg_precision {
 typedef enum pg_kernel {
   PG_KERNEL_AUTO = 0,      /* SPLIT when the shape and precision allow, else GENERAL (ReLU nets: RELU or RELU2
                               in their scopes; every ReLU net outside them runs on GENERAL under AUTO --
-                              RELU_WIDE and RELU2_BLOCK are never picked by AUTO, they are chosen explicitly).  AUTO never sets a
+                              RELU_WIDE and RELU2_BLOCK are never picked by AUTO, they are chosen explicitly, as SIG2 and SIG2_BLOCK are).  AUTO never sets a
                               modifier bit itself; one OR-ed in takes effect where the kernel it picks has the
                               instance (PG_KERNEL_SOLO below), and pg_eval_resolve reports what a call runs */
   PG_KERNEL_GENERAL = 1,   /* one wave per game, f64, any NETWORK_SHAPE */
@@ -163,7 +164,20 @@ typedef enum pg_kernel {
                                 workspace beyond the base.  PG_ERR_UNSUPPORTED for a sigmoid net, any other shape,
                                 no bias, PG_PREC_F64, horizon > 0 and hard_log, and with PG_KERNEL_ADVANCE or
                                 PG_KERNEL_SOLO.  Chosen explicitly only: AUTO never picks it (it runs such
-                                networks on GENERAL) */
+                                networks on GENERAL) */,
+  PG_KERNEL_SIG2_BLOCK = 11  /* PG_ACT_SIGMOID only: [6, 2<=H1<=128, 2<=H2<=128, 2..4] with bias, certified precision,
+                                f32 or f64 genomes, every opponent kind, whole episodes: PG_KERNEL_RELU2_BLOCK's
+                                layout (one 256-thread block per game, 128 threads per paddle's network, a whole
+                                W2 row as f32 in each thread's registers) with sigmoid_f32 in both hidden layers,
+                                PG_KERNEL_SIG2's static bound under the block's chain lengths and its decision
+                                cascade taken by every thread of the block, the rest recomputed in f64 in
+                                numpy's order by the block.  Every frame is stepped (counters
+                                [8] = [12] = 0; [4] the forwards the f32 certificate left undecided, [2] those
+                                recomputed in f64: [2] <= [4] <= [1]); no lane records, no workspace beyond the
+                                base.  PG_ERR_UNSUPPORTED for a ReLU net, any other shape, no bias, PG_PREC_F64,
+                                horizon > 0 and hard_log, and with PG_KERNEL_ADVANCE or PG_KERNEL_SOLO.  Chosen
+                                explicitly only: AUTO never picks it (it runs such networks on WIDE from 64
+                                units up, else on GENERAL) */
 } pg_kernel;
 
 /* pg_eval_args.kernel holds a pg_kernel in its low byte and modifier bits above it (ABI 13).
@@ -178,7 +192,7 @@ enum {
                                and hard_log stay refused); the workspace is the same.  PG_KERNEL_AUTO with the
                                bit resolves exactly as without it: where it picks RELU or RELU2 the advance is
                                on, where it picks SPLIT, WIDE or GENERAL the bit changes nothing.  Every other
-                               explicit kernel with the bit (PG_KERNEL_RELU2_BLOCK among them): PG_ERR_UNSUPPORTED
+                               explicit kernel with the bit (PG_KERNEL_RELU2_BLOCK and PG_KERNEL_SIG2_BLOCK among them): PG_ERR_UNSUPPORTED
                                (checked, like the bits, even for an empty launch).  A launch with trace != NULL records every frame and so
                                runs with the advance off, which is not an error ([8] = [12] = 0) */,
   PG_KERNEL_SOLO = 0x800    /* scripted-opponent games on half a lane group, opt-in: PG_KERNEL_RELU,
@@ -267,7 +281,7 @@ typedef struct pg_eval_args {
                                     timeout at once; [9] hard decisions (see hard_log); split kernel:
                                     [12] serve-delay frames advanced at once (ball hidden); the
                                     episodes' frames = [0] + [8] + [12]; [10], [11], [13..15] 0.
-                                    RELU2_BLOCK steps every frame ([8] = [12] = 0); so do
+                                    RELU2_BLOCK and SIG2_BLOCK step every frame ([8] = [12] = 0); so do
                                     RELU, RELU2 and SIG2 unless
                                     PG_KERNEL_ADVANCE is set on an untraced launch: then [8] and [12]
                                     count as for the split kernel, [0] the stepped frames only, and
@@ -634,6 +648,10 @@ int32_t pg_relu2_block_decide(const pg_relu_decide_args *args, void *stream);
  * f32 output pre-activations; bound [n]: e >= |z32 - numpy's f64 pre-activation| (inf: the network is
  * always decided in f64).  PG_ERR_UNSUPPORTED for a ReLU net, another shape or a net without bias. */
 int32_t pg_sig2_decide(const pg_relu_decide_args *args, void *stream);
+/* The same for k_sig2_block (PG_KERNEL_SIG2_BLOCK): [6, 2..128, 2..128, 2..4] sigmoid networks with bias;
+ * index, stage (0..3), z32 [n, nodes[3]] and bound (pg_sig2_bound.h under its block layout) as
+ * pg_sig2_decide's.  The decision code of a k_sig2_block frame on given inputs, one block per pass. */
+int32_t pg_sig2_block_decide(const pg_relu_decide_args *args, void *stream);
 int32_t pg_physics_reset(int32_t *state, int32_t n, const uint64_t *seeds,
                          const int32_t *one_player, void *stream);
 /* actions [n]: bit0 right up, bit1 right down, bit2 left up, bit3 left down */

@@ -79,7 +79,10 @@ ACTIVATION = "sigmoid"
 # kernel for two-hidden-layer ReLU networks of up to 128 units a layer
 # (ACTIVATION = "relu", NETWORK_SHAPE [6, 2..128, 2..128, 2..4], BIAS), which
 # "auto" leaves on the general kernel above 64 units (it takes
-# no "+advance" or "+solo"); a kernel that cannot run the configured
+# no "+advance" or "+solo"); "sig2_block" is the same for sigmoid networks
+# (ACTIVATION = "sigmoid", the same shapes, BIAS), which "auto" runs on the
+# wide kernel from 64 units up (no "+advance" or "+solo"
+# either); a kernel that cannot run the configured
 # network is an error, never a fallback.  "relu+advance", "relu2+advance",
 # "sig2+advance" and "auto+advance" are the opt-in closed-form frame advance of
 # the certified f32 kernels (serve delays and periodic rallies are not stepped

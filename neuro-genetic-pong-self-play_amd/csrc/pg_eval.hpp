@@ -13,6 +13,8 @@
 //   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
 //   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate (pg_relu2_bound.h, its block layout) with a block per
 //                        game (widths up to 128)
+//   pg_sig2_block.hip    k_sig2_block: k_sig2's certificate (pg_sig2_bound.h, its block layout) on the same layout;
+//                        pg_block2.hpp is what the two block units share
 //   pg_decide.hip        k_decide (pg_decide)
 //   pg_ga.hip            selection, variation, schedule, row gather and hash
 //   pg_gen.hip, pg_hof.hip, pg_pixels.hip    the generation's device steps, the
@@ -232,6 +234,11 @@ int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hi
 // horizon, no hard-case log, no modifier bits
 int32_t relu2_block_scope(const pg_eval_args &a);
 int32_t launch_relu2_block(const EvalParams &p, int dtype, hipStream_t s);
+
+// [6, 2..128, 2..128, 2..4] sigmoid networks with bias on k_sig2_block (pg_sig2_block.hip): k_sig2's
+// certificate and cascade on k_relu2_block's layout; the same scope otherwise
+int32_t sig2_block_scope(const pg_eval_args &a);
+int32_t launch_sig2_block(const EvalParams &p, int dtype, hipStream_t s);
 
 // [6, 2..64, 2..64, 2..4] sigmoid networks with bias on k_sig2 (pg_sig2.hip, pg_hidden2.hpp)
 int32_t sig2_scope(const pg_eval_args &a);

@@ -138,7 +138,7 @@ struct Sig2Bound {
   static __device__ __forceinline__ double unit1(const double w[7]) { return pg_sig2_unit1(w); }
   template <int O>
   static __device__ __forceinline__ void unit2(Sums &s, double p, double w, double bias, const double *w3) {
-    pg_sig2_sums_unit2(&s, p, w, bias, w3, O);
+    pg_sig2_sums_unit2_l(pg_sig2_layout_lanes(), &s, p, w, bias, w3, O);
   }
   template <int LN>
   static __device__ __forceinline__ void reduce(Sums &s) {
@@ -147,7 +147,7 @@ struct Sig2Bound {
   }
   template <int O>
   static __device__ __forceinline__ float finish(const Sums &s, double asum, const double *c) {
-    return pg_sig2_bound_finish(&s, asum, c, O);
+    return pg_sig2_bound_finish_l(pg_sig2_layout_lanes(), &s, asum, c, O);
   }
   template <class Net>
   static __device__ __forceinline__ void set(Net &n, float e) {

@@ -1,6 +1,12 @@
-/* pg_sig2_bound.h -- the static f32 error bound of k_sig2's certificate
- * (pg_hidden2.hpp), in plain C so that it compiles for the device and for the
- * host alike (tests/test_sig2_host.py runs it under gcc).
+/* pg_sig2_bound.h -- the static f32 error bound of the two-hidden-layer
+ * sigmoid certificate, for both layouts that hold such a network: k_sig2's
+ * lanes of a wave (pg_hidden2.hpp) and k_sig2_block's 256-thread block
+ * (pg_sig2_block.hip, pg_block2.hpp).  In plain C so that it compiles for the
+ * device and for the host alike (tests/test_sig2_host.py and
+ * tests/test_sig2_block_host.py run it under gcc).  A layout enters through
+ * its three chain lengths and the constants of its underflow term,
+ * pg_sig2_layout below: the derivation is written out for the lane layout,
+ * and the block layout's lines follow it.
  *
  * The network [6, H1, H2, O] with bias, inputs x_i = k_i / 320 in [0, 1],
  * s(z) = 1 / (1 + e^-z):
@@ -74,6 +80,46 @@
  * in [0, 1] and z^ is finite.  Otherwise e = inf: the certificate and the
  * in-register rules then never decide and the f64 path (numpy's semantics, NaN
  * rule included) does.
+ *
+ * The block layout (k_sig2_block; H1, H2 <= PG_SIG2_BLOCK_MAX_H = 128).  The
+ * derivation above with the chain lengths c1, c2, c3 for 9, 65, 11:
+ *   layer 1  PG_SIG2_BLOCK_CHAIN1 = 9:    1 (gene to f32) + 2 (the feature,
+ *            feat32) + 6 fused multiply-adds
+ *   layer 2  PG_SIG2_BLOCK_CHAIN2 = 129:  1 (gene) + one fused multiply-add
+ *            per (padded) layer-1 unit, 128, onto the bias
+ *   layer 3  PG_SIG2_BLOCK_CHAIN3 = 10:   1 (gene) + 1 (a thread's one
+ *            product W3_ok h2_k) + 6 (the sum over the wave's 64 lanes) + 1 (the
+ *            network's two waves) + 1 (the bias)
+ * (pg_sig2_block.hip asserts them against its code.)
+ *   Q_k = (9 / 4) P_k + (4.5 + 129) B_k,
+ *   S_o = sum_k |W3_ok| (Q_k / 4 + 4.5 + 10) + 10 |b3_o|;
+ * the second-order terms grow with gamma_129 < 2^-16.9 and stay inside the
+ * 2^-16, 2^-15 and 2^-14 factors of the lines above, so inside the 2^-10.
+ * Underflow, line by line for 128 padded units:
+ *   a layer-1 unit: as above, <= 13 eta (1 + u) in z1^_j, a quarter of it in
+ *     h1^_j, plus the sigmoid's <= 6 eta: 13 / 4 + 6 = 9.25 <= 10 eta in h1^_j;
+ *   a layer-2 unit: those through |W2^_kj| (10 eta sum_j |W2_kj|), a flushed W2
+ *     gene times its h1^_j <= 1 (<= 128 of them), the bias conversion and 128
+ *     fmas, each error then carried through at most 128 more roundings
+ *     (257 eta (1 + gamma_129) < 258 eta): <= eta (10 sum_j |W2_kj| + 258) in
+ *     z2^_k, so, with the sigmoid's own <= 6 eta, <= eta (2.5 sum_j |W2_kj| +
+ *     70.5) in h2^_k;
+ *   an output: that through |W3^_ok| (a factor 1 + u): 3 T_o + 72 sum_k |W3_ok|;
+ *     a flushed W3 gene times its h2^_k <= 1 (<= 128 of them); and every
+ *     operation of the layer-3 sum, all of which feed the one output
+ *     (pg_relu2_bound.h's treatment of this layout): the 128 threads' products
+ *     (128 eta), the 127 additions of the tree over the two waves (127 eta;
+ *     exact in the subnormal range with denormals on, as the kernels are
+ *     compiled, and budgeted so that the bound also holds were results
+ *     flushed), the bias conversion and the bias addition (2 eta):
+ *     128 + 128 + 127 + 2 = 385 <= 400:
+ *   underflow = eta (3 max_o T_o + 72 max_o sum_k |W3_ok| + 400).
+ * (The lane layout's lines take a layer-1 unit's share of h1^_j as 7 eta and a
+ * layer-2 unit's constant as 35 where the counts above, taken in full, give
+ * 9.25 and 130 / 4 + 6 = 38.5: the sigmoid's 6 is a count of three operations
+ * of which at most one can flush at a given argument.  Its constants are kept
+ * as they were measured and tested; the block layout's take every line in
+ * full.)
  */
 #ifndef PG_SIG2_BOUND_H
 #define PG_SIG2_BOUND_H
@@ -97,9 +143,34 @@
 #define PG_SIG2_SLOPE 0.25 /* the sigmoid's largest slope */
 #define PG_SIG2_CAP 1e25
 
+#define PG_SIG2_BLOCK_MAX_H 128
+#define PG_SIG2_BLOCK_CHAIN1 9   /* gene + feature (2) + 6 fmas */
+#define PG_SIG2_BLOCK_CHAIN2 129 /* gene + 128 fmas */
+#define PG_SIG2_BLOCK_CHAIN3 10  /* gene + product + 6 lane-sum steps + the two waves + bias */
+
+/* What the bound needs of a layout.  Its instances come by value from the two
+ * functions below, so that every field is a constant where the functions are
+ * inlined. */
+typedef struct pg_sig2_layout {
+  int chain1, chain2, chain3; /* roundings a term of layer 1, 2, 3 passes through */
+  int max_h;                  /* units per hidden layer: what pg_sig2_bound_genome_l accepts */
+  double under_t, under_w3, under_c; /* underflow = eta (under_t max_o T_o + under_w3 max_o sum_k |W3_ok| + under_c) */
+} pg_sig2_layout;
+
+PG_HD pg_sig2_layout pg_sig2_layout_lanes(void) {
+  pg_sig2_layout l = {PG_SIG2_CHAIN1, PG_SIG2_CHAIN2, PG_SIG2_CHAIN3, PG_SIG2_MAX_H, 2.0, 36.0, 80.0};
+  return l;
+}
+
+PG_HD pg_sig2_layout pg_sig2_layout_block(void) {
+  pg_sig2_layout l = {PG_SIG2_BLOCK_CHAIN1, PG_SIG2_BLOCK_CHAIN2, PG_SIG2_BLOCK_CHAIN3, PG_SIG2_BLOCK_MAX_H,
+                      3.0, 72.0, 400.0};
+  return l;
+}
+
 /* Sums over (a share of) the layer-2 units; shares add field by field. */
 typedef struct pg_sig2_sums {
-  double S[PG_SIG2_MAX_OUT];  /* sum_k |W3_ok| (Q_k / 4 + 4.5 + 11) */
+  double S[PG_SIG2_MAX_OUT];  /* sum_k |W3_ok| (Q_k / 4 + 4.5 + c3) */
   double T[PG_SIG2_MAX_OUT];  /* sum_k |W3_ok| sum_j |W2_kj| */
   double W3[PG_SIG2_MAX_OUT]; /* sum_k |W3_ok| */
   double B;                   /* sum_k B_k */
@@ -118,11 +189,13 @@ PG_HD double pg_sig2_unit1(const double w1[7]) {
   return a;
 }
 
-/* One layer-2 unit: p = P_k and w = sum_j |W2_kj| of its row, bias its bias weight, w3 its O output weights. */
-PG_HD void pg_sig2_sums_unit2(pg_sig2_sums *s, double p, double w, double bias, const double *w3, int O) {
+/* One layer-2 unit under layout l: p = P_k and w = sum_j |W2_kj| of its row, bias its bias weight, w3 its O
+ * output weights. */
+PG_HD void pg_sig2_sums_unit2_l(pg_sig2_layout l, pg_sig2_sums *s, double p, double w, double bias, const double *w3,
+                                int O) {
   const double b = w + fabs(bias);
-  const double q = (PG_SIG2_SLOPE * PG_SIG2_CHAIN1) * p + (PG_SIG2_SIG + PG_SIG2_CHAIN2) * b;
-  const double t = PG_SIG2_SLOPE * q + (PG_SIG2_SIG + PG_SIG2_CHAIN3);
+  const double q = (PG_SIG2_SLOPE * l.chain1) * p + (PG_SIG2_SIG + l.chain2) * b;
+  const double t = PG_SIG2_SLOPE * q + (PG_SIG2_SIG + l.chain3);
   for (int o = 0; o < O; ++o) {
     s->S[o] += fabs(w3[o]) * t;
     s->T[o] += fabs(w3[o]) * w;
@@ -132,12 +205,12 @@ PG_HD void pg_sig2_sums_unit2(pg_sig2_sums *s, double p, double w, double bias, 
   s->P += p;
 }
 
-/* The bound from the sums over all layer-2 units, asum = sum_j A_j and the output biases c. */
-PG_HD float pg_sig2_bound_finish(const pg_sig2_sums *s, double asum, const double *c, int O) {
+/* The bound of layout l from the sums over all layer-2 units, asum = sum_j A_j and the output biases c. */
+PG_HD float pg_sig2_bound_finish_l(pg_sig2_layout l, const pg_sig2_sums *s, double asum, const double *c, int O) {
   double smax = 0.0, tmax = 0.0, w3max = 0.0;
   int ok = asum <= PG_SIG2_CAP && s->B <= PG_SIG2_CAP && s->P <= PG_SIG2_CAP; /* false for NaN */
   for (int o = 0; o < O; ++o) {
-    const double so = s->S[o] + PG_SIG2_CHAIN3 * fabs(c[o]);
+    const double so = s->S[o] + l.chain3 * fabs(c[o]);
     ok = ok && so <= PG_SIG2_CAP && s->T[o] <= PG_SIG2_CAP && s->W3[o] <= PG_SIG2_CAP;
     smax = so > smax ? so : smax;
     tmax = s->T[o] > tmax ? s->T[o] : tmax;
@@ -145,16 +218,18 @@ PG_HD float pg_sig2_bound_finish(const pg_sig2_sums *s, double asum, const doubl
   }
   if (!ok) return (float)INFINITY;
   const double u = 0x1.0p-24, eta = 0x1.0p-126;
-  const double under = eta * (2.0 * tmax + 36.0 * w3max + 80.0);
+  const double under = eta * (l.under_t * tmax + l.under_w3 * w3max + l.under_c);
   return (float)((u * smax + under) * (1.0 + 0x1.0p-10));
 }
 
-/* The whole bound of one genome (numpy_nn.py:52-69 layout with bias: W1
- * [H1, 7], W2 [H2, H1 + 1], W3 [O, H2 + 1], bias columns last), serially:
- * what a test or a host tool calls; k_sig2's lanes run the same functions on
- * their shares.  H1 <= PG_SIG2_MAX_H. */
-PG_HD float pg_sig2_bound_genome(const double *g, int H1, int H2, int O) {
-  double A[PG_SIG2_MAX_H], asum = 0.0, c[PG_SIG2_MAX_OUT];
+/* The whole bound of one genome under layout l (numpy_nn.py:52-69 layout with
+ * bias: W1 [H1, 7], W2 [H2, H1 + 1], W3 [O, H2 + 1], bias columns last),
+ * serially: what a test or a host tool calls; k_sig2's lanes and k_sig2_block's
+ * threads run the same functions on their shares.  A network wider than the
+ * layout holds (H1 or H2 > l.max_h) has no bound: inf. */
+PG_HD float pg_sig2_bound_genome_l(pg_sig2_layout l, const double *g, int H1, int H2, int O) {
+  double A[PG_SIG2_BLOCK_MAX_H], asum = 0.0, c[PG_SIG2_MAX_OUT]; /* the larger layout's */
+  if (H1 > l.max_h || H2 > l.max_h || l.max_h > PG_SIG2_BLOCK_MAX_H) return (float)INFINITY;
   const double *w2 = g + (long)H1 * 7, *w3 = w2 + (long)H2 * (H1 + 1);
   pg_sig2_sums s;
   pg_sig2_sums_init(&s);
@@ -170,10 +245,23 @@ PG_HD float pg_sig2_bound_genome(const double *g, int H1, int H2, int O) {
       w += fabs(row[j]);
     }
     for (int o = 0; o < O; ++o) v[o] = w3[(long)o * (H2 + 1) + k];
-    pg_sig2_sums_unit2(&s, p, w, row[H1], v, O);
+    pg_sig2_sums_unit2_l(l, &s, p, w, row[H1], v, O);
   }
   for (int o = 0; o < O; ++o) c[o] = w3[(long)o * (H2 + 1) + H2];
-  return pg_sig2_bound_finish(&s, asum, c, O);
+  return pg_sig2_bound_finish_l(l, &s, asum, c, O);
+}
+
+/* The lane layout's, under their earlier names and signatures (k_sig2, pg_hidden2.hpp; H1 <= PG_SIG2_MAX_H). */
+PG_HD void pg_sig2_sums_unit2(pg_sig2_sums *s, double p, double w, double bias, const double *w3, int O) {
+  pg_sig2_sums_unit2_l(pg_sig2_layout_lanes(), s, p, w, bias, w3, O);
+}
+
+PG_HD float pg_sig2_bound_finish(const pg_sig2_sums *s, double asum, const double *c, int O) {
+  return pg_sig2_bound_finish_l(pg_sig2_layout_lanes(), s, asum, c, O);
+}
+
+PG_HD float pg_sig2_bound_genome(const double *g, int H1, int H2, int O) {
+  return pg_sig2_bound_genome_l(pg_sig2_layout_lanes(), g, H1, H2, O);
 }
 
 #endif /* PG_SIG2_BOUND_H */

@@ -24,6 +24,7 @@
 //   k_sig2<LN,U1,U2,O,WT>   [6, H1<=64, H2<=64, O] sigmoid networks (pg_sig2.hip, pg_hidden2.hpp).
 //                         These three share one game loop (pg_certgame.hpp).
 //   k_relu2_block<O,WT>   [6, H1<=128, H2<=128, O] ReLU networks, a block per game (pg_relu2_block.hip).
+//   k_sig2_block<O,WT>    [6, H1<=128, H2<=128, O] sigmoid networks, a block per game (pg_sig2_block.hip).
 //   k_fitness             sum(all_rewards) / GAMES_TO_PLAY in the reference order.
 //   k_forward_resident, k_physics_*   pg_forward's certified path and the SoA
 //                         Pong stepper (pg_physics_*): here because k_service's
@@ -449,7 +450,7 @@ static int32_t check_modifier_bits(int kernel, bool advance, bool solo) {
 
 // Scope (pg_eval.hpp: each family states its own, activation first).  When a
 // kernel is asked is today's order of refusals, an asymmetry that is kept:
-// RELU2, RELU_WIDE, SIG2 and RELU2_BLOCK are refused out of scope on entry, even
+// RELU2, RELU_WIDE, SIG2, RELU2_BLOCK and SIG2_BLOCK are refused out of scope on entry, even
 // for an empty launch (scope_on_entry); RELU, SPLIT and WIDE only after the
 // n_genomes == 0 return -- for a network of the other activation before the
 // workspace check (scope_of_activation), for the rest at the launch (launch_games).
@@ -458,6 +459,7 @@ static int32_t scope_on_entry(const pg_eval_args &a) {
   if (a.kernel == PG_KERNEL_RELU_WIDE) return wide_scope(a, true);
   if (a.kernel == PG_KERNEL_SIG2) return sig2_scope(a);
   if (a.kernel == PG_KERNEL_RELU2_BLOCK) return relu2_block_scope(a);
+  if (a.kernel == PG_KERNEL_SIG2_BLOCK) return sig2_block_scope(a);
   return PG_OK;
 }
 
@@ -537,7 +539,8 @@ static EvalParams eval_params(const pg_eval_args *a) {
   return p;
 }
 
-// the games on kernel (resolve_kernel's); RELU_WIDE, RELU2, SIG2 and RELU2_BLOCK were found in scope on entry
+// the games on kernel (resolve_kernel's); RELU_WIDE, RELU2, SIG2, RELU2_BLOCK and SIG2_BLOCK were found in scope
+// on entry
 // (advance, solo: modifiers_in_effect's)
 static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bool advance, bool solo, hipStream_t s) {
   void *const after_base = (char *)a->workspace + eval_base_workspace(a);
@@ -571,6 +574,8 @@ static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bo
       return launch_sig2(p, dtype, advance, solo, s);
     case PG_KERNEL_RELU2_BLOCK:
       return launch_relu2_block(p, dtype, s);
+    case PG_KERNEL_SIG2_BLOCK:
+      return launch_sig2_block(p, dtype, s);
     case PG_KERNEL_GENERAL:
       return launch_general(p, dtype, s);
     default:

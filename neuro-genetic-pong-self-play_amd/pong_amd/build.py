@@ -28,7 +28,8 @@ UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_general", "pg_general.hip", []), (
          ("pg_hof_scan", "pg_hof_scan.cpp", []), ("pg_wide", "pg_wide.hip", []), ("pg_pixels", "pg_pixels.hip", []),
          ("pg_hof", "pg_hof.hip", []), ("pg_gen", "pg_gen.hip", []), ("pg_decide", "pg_decide.hip", []),
          ("pg_relu", "pg_relu.hip", []), ("pg_relu2", "pg_relu2.hip", []),
-         ("pg_relu2_block", "pg_relu2_block.hip", []), ("pg_sig2", "pg_sig2.hip", []), ("pg_relu_solo", "pg_relu.hip", ["-DPG_SOLO_UNIT"]),
+         ("pg_relu2_block", "pg_relu2_block.hip", []), ("pg_sig2_block", "pg_sig2_block.hip", []),
+         ("pg_sig2", "pg_sig2.hip", []), ("pg_relu_solo", "pg_relu.hip", ["-DPG_SOLO_UNIT"]),
          ("pg_relu2_solo", "pg_relu2.hip", ["-DPG_SOLO_UNIT"]), ("pg_sig2_solo", "pg_sig2.hip", ["-DPG_SOLO_UNIT"]),
          ("pg_service_solo", "pg_service_solo.hip", []),
          ("pg_service_solo_o3", "pg_service_solo.hip", ["-DPG_SOLO_O3"] + _ILP)] + [

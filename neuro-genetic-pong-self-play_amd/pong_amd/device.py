@@ -29,16 +29,18 @@ MODIFIERS = {"advance": L.PG_KERNEL_ADVANCE, "solo": L.PG_KERNEL_SOLO}
 MODIFIED = ("relu", "relu2", "sig2", "auto")  # the bases either modifier goes with
 # kernels chosen by name only, without modifiers: kernel_code and kernel_name consult this mapping after KERNELS
 MORE_KERNELS = {"relu2_block": L.PG_KERNEL_RELU2_BLOCK}
+# the block-per-game kernels added since (the two mappings above are pinned by their tests): the same rules
+BLOCK_KERNELS = {"sig2_block": L.PG_KERNEL_SIG2_BLOCK}
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
 
 def kernel_code(name: str) -> int:
     """pg_eval_args.kernel for a kernel name: a key of ``KERNELS`` without "+"
-    or of ``MORE_KERNELS``, optionally followed by "+advance" and "+solo" in
+    , of ``MORE_KERNELS`` or of ``BLOCK_KERNELS``, optionally followed by "+advance" and "+solo" in
     either order, each at most once and only on relu, relu2, sig2 and auto
     (KeyError otherwise)."""
     base, *mods = str(name).split("+")
-    known = {**KERNELS, **MORE_KERNELS}
+    known = {**KERNELS, **MORE_KERNELS, **BLOCK_KERNELS}
     ok = base in known and (not mods or base in MODIFIED) and len(set(mods)) == len(mods)
     if not ok or any(m not in MODIFIERS for m in mods):
         raise KeyError(f"kernel {name!r}: valid are {sorted(k for k in known if '+' not in k)}, and "
@@ -54,7 +56,7 @@ def kernel_name(code: int) -> str:
     "+advance" and "+solo" for the modifier bits in effect.  A reported name need
     not be one kernel_code accepts: "split+solo" is what "auto+solo" runs on a
     [6, 64, 3] sigmoid network."""
-    names = {v: k for k, v in {**KERNELS, **MORE_KERNELS}.items() if "+" not in k}
+    names = {v: k for k, v in {**KERNELS, **MORE_KERNELS, **BLOCK_KERNELS}.items() if "+" not in k}
     return names[code & 0xff] + "".join("+" + m for m, bit in MODIFIERS.items() if code & bit)
 
 
@@ -404,6 +406,12 @@ class Evaluator:
         pre-activations, bound [n] f32 on |z32 - numpy's f64 pre-activation|;
         inf = the network is always decided in f64)."""
         return self._relu_decide("pg_sig2_decide", genomes, k, genome_index)
+
+    def sig2_block_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The same for the block-per-game sigmoid kernel (pg_sig2_block_decide:
+        k_sig2_block's decision code, [6, 2..128, 2..128, 2..4] sigmoid networks
+        with bias; stages 0..3 and the bound of the block layout)."""
+        return self._relu_decide("pg_sig2_block_decide", genomes, k, genome_index)
 
     def _relu_decide(self, entry: str, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor]):
         dev = self.device
