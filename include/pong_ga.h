@@ -33,7 +33,8 @@
  *                                the "alternative activation function" of numpy_nn.py:26)
  * pg_relu2_decide                the same, as k_relu2 decides it (ReLU networks with two hidden layers)
  * pg_relu2_block_decide          the same, as k_relu2_block decides it (two hidden layers of up to 128 units)
- * pg_relu_wide_decide            the same, as k_wide's ReLU instances decide it (wide ReLU networks)
+ * pg_relu3_decide                the same, as k_relu3 decides it (ReLU networks with three hidden layers)
+ * pg_relu_wide_decide           the same, as k_wide's ReLU instances decide it (wide ReLU networks)
  * pg_sig2_decide                 the same, as k_sig2 decides it (sigmoid networks with two hidden layers)
  * pg_sig2_block_decide           the same, as k_sig2_block decides it (two hidden layers of up to 128 units)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
@@ -177,14 +178,26 @@ typedef enum pg_kernel {
                                 base.  PG_ERR_UNSUPPORTED for a ReLU net, any other shape, no bias, PG_PREC_F64,
                                 horizon > 0 and hard_log, and with PG_KERNEL_ADVANCE or PG_KERNEL_SOLO.  Chosen
                                 explicitly only: AUTO never picks it (it runs such networks on WIDE from 64
-                                units up, else on GENERAL) */
+                                units up, else on GENERAL) */,
+  PG_KERNEL_RELU3 = 12       /* PG_ACT_RELU only: [6, 2<=H1<=32, 2<=H2<=32, 2<=H3<=32, 2..4] (three hidden layers)
+                                with bias, certified precision, f32 or f64 genomes, every opponent kind, whole
+                                episodes, traced or untraced: k_relu2's layout and certificate one layer deeper
+                                 -- all four layers' f32 weights resident for the game on a half-group
+                                of 8 lanes (widths up to 16) or 16 lanes, layer 1's and layer 2's activations
+                                all-gathered through LDS each frame, the decisions its static f32 bound cannot
+                                prove recomputed in f64 in numpy's order.  Every frame is stepped (counters
+                                [8] = [12] = 0) unless PG_KERNEL_ADVANCE is set; PG_KERNEL_SOLO applies as to
+                                PG_KERNEL_RELU2; no lane records, no workspace beyond the base.
+                                PG_ERR_UNSUPPORTED for a sigmoid net, any other shape, no bias, PG_PREC_F64,
+                                horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it (it runs
+                                such networks on GENERAL, with or without modifier bits) */
 } pg_kernel;
 
 /* pg_eval_args.kernel holds a pg_kernel in its low byte and modifier bits above it (ABI 13).
  * Any bit other than the ones named here: PG_ERR_INVALID. */
 enum {
   PG_KERNEL_ADVANCE = 0x100 /* closed-form frame advance on the certified f32 families, opt-in:
-                               PG_KERNEL_RELU, PG_KERNEL_RELU2 and PG_KERNEL_SIG2 step every frame; with this bit
+                               PG_KERNEL_RELU, PG_KERNEL_RELU2, PG_KERNEL_SIG2 and PG_KERNEL_RELU3 step every frame; with this bit
                                OR-ed in they advance a serve delay's 29 hidden-ball frames at once (counters [12])
                                and jump the rest of a rally proven periodic to its timeout frame (counters [8]),
                                as SPLIT and WIDE always do -- every output bit for bit the stepping kernel's.
@@ -196,7 +209,7 @@ enum {
                                (checked, like the bits, even for an empty launch).  A launch with trace != NULL records every frame and so
                                runs with the advance off, which is not an error ([8] = [12] = 0) */,
   PG_KERNEL_SOLO = 0x800    /* scripted-opponent games on half a lane group, opt-in: PG_KERNEL_RELU,
-                               PG_KERNEL_RELU2 and PG_KERNEL_SIG2 give every game a group of 2 LN lanes, of which
+                               PG_KERNEL_RELU2, PG_KERNEL_SIG2 and PG_KERNEL_RELU3 give every game a group of 2 LN lanes, of which
                                the left paddle's half idles against PG_OPP_HARDCODED, PG_OPP_ROM_CPU and
                                PG_OPP_SCORE.  With this bit OR-ed in such a game is played by one half-group alone
                                and only a PG_OPP_NN game takes a whole group -- every output and all 16 counters
@@ -240,7 +253,7 @@ typedef struct pg_net {
   int32_t bias;                  /* 1 = BIAS, weight rows are (in + 1) wide */
   int32_t dtype;                 /* pg_dtype of genomes and opponents */
   int32_t activation;            /* ABI 13: pg_activation; 0 (a zero-initialised net) = the sigmoid.  ReLU
-                                    networks run on PG_KERNEL_RELU / PG_KERNEL_RELU2 / PG_KERNEL_RELU2_BLOCK / PG_KERNEL_RELU_WIDE / PG_KERNEL_GENERAL and pg_forward (always
+                                    networks run on PG_KERNEL_RELU / PG_KERNEL_RELU2 / PG_KERNEL_RELU3 / PG_KERNEL_RELU2_BLOCK / PG_KERNEL_RELU_WIDE / PG_KERNEL_GENERAL and pg_forward (always
                                     f64) only: pg_decide, pg_wide_decide, PG_KERNEL_SPLIT, PG_KERNEL_WIDE,
                                     horizon > 0 and hard_log return PG_ERR_UNSUPPORTED for them */
 } pg_net;
@@ -641,6 +654,10 @@ int32_t pg_relu2_decide(const pg_relu_decide_args *args, void *stream);
  * index, stage (0 certified, 1 f64), z32 [n, nodes[3]] and bound as pg_relu2_decide's.  The decision code
  * of a k_relu2_block frame on given inputs, one block per pass. */
 int32_t pg_relu2_block_decide(const pg_relu_decide_args *args, void *stream);
+/* The same for k_relu3 (PG_KERNEL_RELU3): [6, 2..32, 2..32, 2..32, 2..4] ReLU networks with bias; index,
+ * stage (0 certified, 1 f64) and bound as pg_relu2_decide's, z32 is [n, nodes[4]].  The decision code of a
+ * k_relu3 frame on given inputs. */
+int32_t pg_relu3_decide(const pg_relu_decide_args *args, void *stream);
 /* The decision code of a k_sig2 frame (PG_KERNEL_SIG2) on given inputs: PG_ACT_SIGMOID networks
  * [6, 2..64, 2..64, 2..4] with bias, the argument struct of pg_relu_decide.  index [n]: the argmax of
  * numpy's f64 sigmoid outputs; stage [n]: 0 the f32 certificate (certify_c under the network's static

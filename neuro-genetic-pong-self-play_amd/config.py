@@ -82,7 +82,10 @@ ACTIVATION = "sigmoid"
 # no "+advance" or "+solo"); "sig2_block" is the same for sigmoid networks
 # (ACTIVATION = "sigmoid", the same shapes, BIAS), which "auto" runs on the
 # wide kernel from 64 units up (no "+advance" or "+solo"
-# either); a kernel that cannot run the configured
+# either); "relu3" is the opt-in certified f32 kernel for three-hidden-layer
+# ReLU networks (ACTIVATION = "relu", NETWORK_SHAPE [6, 2..32, 2..32, 2..32,
+# 2..4], BIAS), which "auto" leaves on the general kernel (it
+# takes "+advance" and "+solo" as "relu2" does); a kernel that cannot run the configured
 # network is an error, never a fallback.  "relu+advance", "relu2+advance",
 # "sig2+advance" and "auto+advance" are the opt-in closed-form frame advance of
 # the certified f32 kernels (serve delays and periodic rallies are not stepped

@@ -1,5 +1,5 @@
 // pg_certgame.hpp -- what the certified f32 kernel families share: k_relu
-// (pg_relu.hip), k_relu2 (pg_relu2.hip) and k_sig2 (pg_sig2.hip) are thin
+// (pg_relu.hip), k_relu2 (pg_relu2.hip), k_sig2 (pg_sig2.hip) and k_relu3 (pg_relu3.hip) are thin
 // __global__ wrappers of the one game loop cert_game<P, kAdvance, kSolo>, and
 // k_relu_decide, k_relu2_decide and k_sig2_decide of the one pass
 // cert_decide_pass<P>.  k_relu_adv, k_relu2_adv and k_sig2_adv wrap the same
@@ -13,6 +13,8 @@
 //   Net              a network's weights and bound as f32 in VGPRs; Net::e is
 //                    the bound pg_*_decide reports
 //   Lds              one half-group's __shared__ element
+//   Dims, dims(params)   optional: the policy's own hidden sizes in place of
+//                    CertDims (cert_dims below; k_relu3, pg_hidden3.hpp)
 //   load(net, g, dims, lds, hl)       this lane's share of genome g, in place
 //   decide(net, g, dims, k, live, lds, hl, z, stage)   one frame's np.argmax
 //                    index on the doubled-centroid features k; z: the f32
@@ -25,6 +27,7 @@
 #include <stdint.h>
 
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/pong_ga.h"
 #include "pg_cascade.hpp"
@@ -49,6 +52,23 @@ struct CertDecideParams {
   float *bound;
   int64_t gstride;
   int n, H1, H2;
+};
+
+// The hidden sizes as a policy's load and decide take them, from a launch's
+// parameters: CertDims, unless the policy names its own (P::Dims, made by
+// P::dims(params): k_relu3's three widths, pg_hidden3.hpp) -- so the structs
+// above, and with them the other families' kernels, stay what they are.
+template <class P, class = void>
+struct cert_dims {
+  static __device__ __forceinline__ CertDims of(const EvalParams &p) { return {p.nodes[1], p.nodes[2]}; }
+  static __device__ __forceinline__ CertDims of(const CertDecideParams &p) { return {p.H1, p.H2}; }
+};
+template <class P>
+struct cert_dims<P, std::void_t<typename P::Dims>> {
+  template <class Params>
+  static __device__ __forceinline__ typename P::Dims of(const Params &p) {
+    return P::dims(p);
+  }
 };
 
 // kAdvance's per-group record (with kSolo: per half-group): Brent's saved rally
@@ -132,7 +152,7 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
   typename P::Lds &lds = lds_all[threadIdx.x / LN];
   const WT *genomes = (const WT *)p.genomes;
   const WT *opponents = (const WT *)p.opponents;
-  const CertDims dims = {p.nodes[1], p.nodes[2]};
+  const auto dims = cert_dims<P>::of(p);
   const int games_total = active_total(p);
   // per lane: far below 2^32.  c_fail (stage > 0) is c_f64 itself where the
   // stages are 0/1: a counter of its own there costs the frame loop registers
@@ -364,14 +384,15 @@ __device__ __forceinline__ void cert_game(const EvalParams &params) {
 // pass; a block's pass decides rows [base, base + 256 / LN).  The grid-stride
 // loop over base is the kernels' own: with the loop in here, inlining moves a
 // kernel's exit block and with it the instruction counts.
-template <class P>
-__device__ __forceinline__ void cert_decide_pass(const CertDecideParams &p, long base) {
+// (Params: CertDecideParams, or a family's extension of it)
+template <class P, class Params>
+__device__ __forceinline__ void cert_decide_pass(const Params &p, long base) {
   using WT = typename P::WT;
   constexpr int LN = P::LN, O = P::O, HPB = 256 / LN;
   __shared__ typename P::Lds lds_all[HPB];
   const int hg = threadIdx.x / LN, hl = threadIdx.x & (LN - 1);
   const WT *genomes = (const WT *)p.genomes;
-  const CertDims dims = {p.H1, p.H2};
+  const auto dims = cert_dims<P>::of(p);
   const long t = base + hg;
   if (t < p.n) {
     const WT *g = genomes + (long)(p.gidx ? p.gidx[t] : t) * p.gstride;

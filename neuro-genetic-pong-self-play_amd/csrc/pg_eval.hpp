@@ -11,6 +11,7 @@
 //   pg_general.hip       the f64 path: k_general, pg_forward with k_forward_general
 //   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
 //   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
+//   pg_relu3.hip         k_relu3: the certified f32 family for three hidden ReLU layers (pg_hidden3.hpp)
 //   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate (pg_relu2_bound.h, its block layout) with a block per
 //                        game (widths up to 128)
 //   pg_sig2_block.hip    k_sig2_block: k_sig2's certificate (pg_sig2_bound.h, its block layout) on the same layout;
@@ -229,6 +230,11 @@ bool relu2_shape_ok(const pg_net &n);
 int32_t relu2_scope(const pg_eval_args &a);
 int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
+// [6, 2..32, 2..32, 2..32, 2..4] ReLU networks with bias on k_relu3 (pg_relu3.hip, pg_hidden3.hpp): the
+// same for three hidden layers
+int32_t relu3_scope(const pg_eval_args &a);
+int32_t launch_relu3(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
+
 // [6, 2..128, 2..128, 2..4] ReLU networks with bias on k_relu2_block (pg_relu2_block.hip): k_relu2's
 // certificate with a 256-thread block per game; certified precision, no workspace beyond the base, no
 // horizon, no hard-case log, no modifier bits
@@ -249,5 +255,6 @@ int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hip
 void relu_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 void relu2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 void sig2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
+void relu3_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 
 }  // namespace pg

@@ -377,7 +377,8 @@ static size_t split_records_bytes(const pg_eval_args *a) {
 // the closed-form advance on the certified f32 families' untraced launches, solo games on theirs and
 // on SPLIT's in split_solo_scope (the bit reaches SPLIT through PG_KERNEL_AUTO only: check_modifier_bits)
 static int modifiers_in_effect(int kernel, const pg_eval_args &a, bool advance, bool solo) {
-  const bool cert = kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2;
+  const bool cert = kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2 ||
+                    kernel == PG_KERNEL_RELU3;
   int bits = 0;
   if (advance && cert && !a.trace) bits |= PG_KERNEL_ADVANCE;
   if (solo && (cert || (kernel == PG_KERNEL_SPLIT && split_solo_scope(a)))) bits |= PG_KERNEL_SOLO;
@@ -433,7 +434,8 @@ static int32_t check_eval_ranges(const pg_eval_args *a) {
 // PG_KERNEL_ADVANCE and PG_KERNEL_SOLO go with the certified families' kernels, named or through AUTO
 // (SPLIT takes the solo bit through AUTO only: the refusal of an explicit SPLIT | SOLO is kept for now)
 static bool takes_modifier_bits(int kernel) {
-  return kernel == PG_KERNEL_AUTO || kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2;
+  return kernel == PG_KERNEL_AUTO || kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2 ||
+         kernel == PG_KERNEL_RELU3;  // (RELU3 joined after the refusals' messages below were recorded)
 }
 
 static int32_t check_modifier_bits(int kernel, bool advance, bool solo) {
@@ -460,6 +462,7 @@ static int32_t scope_on_entry(const pg_eval_args &a) {
   if (a.kernel == PG_KERNEL_SIG2) return sig2_scope(a);
   if (a.kernel == PG_KERNEL_RELU2_BLOCK) return relu2_block_scope(a);
   if (a.kernel == PG_KERNEL_SIG2_BLOCK) return sig2_block_scope(a);
+  if (a.kernel == PG_KERNEL_RELU3) return relu3_scope(a);
   return PG_OK;
 }
 
@@ -576,6 +579,8 @@ static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bo
       return launch_relu2_block(p, dtype, s);
     case PG_KERNEL_SIG2_BLOCK:
       return launch_sig2_block(p, dtype, s);
+    case PG_KERNEL_RELU3:
+      return launch_relu3(p, dtype, advance, solo, s);
     case PG_KERNEL_GENERAL:
       return launch_general(p, dtype, s);
     default:

@@ -26,21 +26,25 @@ ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 # the modifiers a kernel name may carry after "+" (kernel_code); "+solo" (PG_KERNEL_SOLO): the same
 # families play a game against a scripted opponent on half a lane group, with the same results
 MODIFIERS = {"advance": L.PG_KERNEL_ADVANCE, "solo": L.PG_KERNEL_SOLO}
-MODIFIED = ("relu", "relu2", "sig2", "auto")  # the bases either modifier goes with
+MODIFIED = ("relu", "relu2", "sig2", "auto", "relu3")  # the bases either modifier goes with
 # kernels chosen by name only, without modifiers: kernel_code and kernel_name consult this mapping after KERNELS
 MORE_KERNELS = {"relu2_block": L.PG_KERNEL_RELU2_BLOCK}
 # the block-per-game kernels added since (the two mappings above are pinned by their tests): the same rules
 BLOCK_KERNELS = {"sig2_block": L.PG_KERNEL_SIG2_BLOCK}
+# the certified f32 families added since (the three mappings above are pinned by their tests): chosen by
+# name only, and a base of MODIFIED
+DEEP_KERNELS = {"relu3": L.PG_KERNEL_RELU3}
+_NAMED = (KERNELS, MORE_KERNELS, BLOCK_KERNELS, DEEP_KERNELS)  # what kernel_code and kernel_name consult, in this order
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
 
 def kernel_code(name: str) -> int:
     """pg_eval_args.kernel for a kernel name: a key of ``KERNELS`` without "+"
-    , of ``MORE_KERNELS`` or of ``BLOCK_KERNELS``, optionally followed by "+advance" and "+solo" in
-    either order, each at most once and only on relu, relu2, sig2 and auto
+    , of ``MORE_KERNELS``, of ``BLOCK_KERNELS`` or of ``DEEP_KERNELS``, optionally followed by "+advance"
+    and "+solo" in either order, each at most once and only on relu, relu2, sig2, relu3 and auto
     (KeyError otherwise)."""
     base, *mods = str(name).split("+")
-    known = {**KERNELS, **MORE_KERNELS, **BLOCK_KERNELS}
+    known = {k: v for mapping in _NAMED for k, v in mapping.items()}
     ok = base in known and (not mods or base in MODIFIED) and len(set(mods)) == len(mods)
     if not ok or any(m not in MODIFIERS for m in mods):
         raise KeyError(f"kernel {name!r}: valid are {sorted(k for k in known if '+' not in k)}, and "
@@ -56,7 +60,7 @@ def kernel_name(code: int) -> str:
     "+advance" and "+solo" for the modifier bits in effect.  A reported name need
     not be one kernel_code accepts: "split+solo" is what "auto+solo" runs on a
     [6, 64, 3] sigmoid network."""
-    names = {v: k for k, v in {**KERNELS, **MORE_KERNELS, **BLOCK_KERNELS}.items() if "+" not in k}
+    names = {v: k for mapping in _NAMED for k, v in mapping.items() if "+" not in k}
     return names[code & 0xff] + "".join("+" + m for m, bit in MODIFIERS.items() if code & bit)
 
 
@@ -396,6 +400,11 @@ class Evaluator:
         """The same for the block-per-game ReLU kernel (pg_relu2_block_decide:
         k_relu2_block's decision code, [6, 2..128, 2..128, 2..4] networks with bias)."""
         return self._relu_decide("pg_relu2_block_decide", genomes, k, genome_index)
+
+    def relu3_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The same for the three-hidden-layer ReLU kernel (pg_relu3_decide:
+        k_relu3's decision code, [6, 2..32, 2..32, 2..32, 2..4] networks with bias)."""
+        return self._relu_decide("pg_relu3_decide", genomes, k, genome_index)
 
     def sig2_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
         """The two-hidden-layer sigmoid kernel's own decision (pg_sig2_decide:
