@@ -37,6 +37,7 @@
  * pg_relu_wide_decide           the same, as k_wide's ReLU instances decide it (wide ReLU networks)
  * pg_sig2_decide                 the same, as k_sig2 decides it (sigmoid networks with two hidden layers)
  * pg_sig2_block_decide           the same, as k_sig2_block decides it (two hidden layers of up to 128 units)
+ * pg_sig3_decide                 the same, as k_sig3 decides it (sigmoid networks with three hidden layers)
  * pg_physics_reset/pg_physics_step  env.reset()/env.step(action) main.py:56,77
  *                                (the build's SoA Pong; the emulator is absent)
  * pg_ga_select_tournament        tools.selTournament (ga.py:94; DEAP)
@@ -190,6 +191,20 @@ typedef enum pg_kernel {
                                 PG_KERNEL_RELU2; no lane records, no workspace beyond the base.
                                 PG_ERR_UNSUPPORTED for a sigmoid net, any other shape, no bias, PG_PREC_F64,
                                 horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it (it runs
+                                such networks on GENERAL, with or without modifier bits) */,
+  PG_KERNEL_SIG3 = 13        /* PG_ACT_SIGMOID only: [6, 2<=H1<=32, 2<=H2<=32, 2<=H3<=32, 2..4] (three hidden layers)
+                                with bias, certified precision, f32 or f64 genomes, every opponent kind, whole
+                                episodes, n_games 1..64, traced or untraced: PG_KERNEL_RELU3's layout (all four
+                                layers' f32 weights resident for the game on a half-group of 8 or 16 lanes, layer
+                                1's and layer 2's activations all-gathered through LDS each frame) with
+                                sigmoid_f32 in the three hidden layers, a static f32 bound through three sigmoid
+                                layers and PG_KERNEL_SIG2's decision cascade: counters [4] the
+                                forwards the f32 certificate left undecided, [2] those recomputed in f64 in
+                                numpy's order ([2] <= [4] <= [1]).  Every frame is stepped (counters
+                                [8] = [12] = 0) unless PG_KERNEL_ADVANCE is set; PG_KERNEL_SOLO applies as to
+                                PG_KERNEL_SIG2; no lane records, no workspace beyond the base.
+                                PG_ERR_UNSUPPORTED for a ReLU net, any other shape, no bias, PG_PREC_F64,
+                                horizon > 0 and hard_log.  Chosen explicitly only: AUTO never picks it (it runs
                                 such networks on GENERAL, with or without modifier bits) */
 } pg_kernel;
 
@@ -197,7 +212,7 @@ typedef enum pg_kernel {
  * Any bit other than the ones named here: PG_ERR_INVALID. */
 enum {
   PG_KERNEL_ADVANCE = 0x100 /* closed-form frame advance on the certified f32 families, opt-in:
-                               PG_KERNEL_RELU, PG_KERNEL_RELU2, PG_KERNEL_SIG2 and PG_KERNEL_RELU3 step every frame; with this bit
+                               PG_KERNEL_RELU, PG_KERNEL_RELU2, PG_KERNEL_SIG2, PG_KERNEL_RELU3 and PG_KERNEL_SIG3 step every frame; with this bit
                                OR-ed in they advance a serve delay's 29 hidden-ball frames at once (counters [12])
                                and jump the rest of a rally proven periodic to its timeout frame (counters [8]),
                                as SPLIT and WIDE always do -- every output bit for bit the stepping kernel's.
@@ -209,7 +224,7 @@ enum {
                                (checked, like the bits, even for an empty launch).  A launch with trace != NULL records every frame and so
                                runs with the advance off, which is not an error ([8] = [12] = 0) */,
   PG_KERNEL_SOLO = 0x800    /* scripted-opponent games on half a lane group, opt-in: PG_KERNEL_RELU,
-                               PG_KERNEL_RELU2, PG_KERNEL_SIG2 and PG_KERNEL_RELU3 give every game a group of 2 LN lanes, of which
+                               PG_KERNEL_RELU2, PG_KERNEL_SIG2, PG_KERNEL_RELU3 and PG_KERNEL_SIG3 give every game a group of 2 LN lanes, of which
                                the left paddle's half idles against PG_OPP_HARDCODED, PG_OPP_ROM_CPU and
                                PG_OPP_SCORE.  With this bit OR-ed in such a game is played by one half-group alone
                                and only a PG_OPP_NN game takes a whole group -- every output and all 16 counters
@@ -669,6 +684,10 @@ int32_t pg_sig2_decide(const pg_relu_decide_args *args, void *stream);
  * index, stage (0..3), z32 [n, nodes[3]] and bound (pg_sig2_bound.h under its block layout) as
  * pg_sig2_decide's.  The decision code of a k_sig2_block frame on given inputs, one block per pass. */
 int32_t pg_sig2_block_decide(const pg_relu_decide_args *args, void *stream);
+/* The same for k_sig3 (PG_KERNEL_SIG3): [6, 2..32, 2..32, 2..32, 2..4] sigmoid networks with bias; index,
+ * stage (0..3) and bound (pg_sig3_bound.h) as pg_sig2_decide's, z32 is [n, nodes[4]].  The decision code of
+ * a k_sig3 frame on given inputs. */
+int32_t pg_sig3_decide(const pg_relu_decide_args *args, void *stream);
 int32_t pg_physics_reset(int32_t *state, int32_t n, const uint64_t *seeds,
                          const int32_t *one_player, void *stream);
 /* actions [n]: bit0 right up, bit1 right down, bit2 left up, bit3 left down */

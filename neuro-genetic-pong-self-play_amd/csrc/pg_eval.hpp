@@ -12,6 +12,7 @@
 //   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
 //   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
 //   pg_relu3.hip         k_relu3: the certified f32 family for three hidden ReLU layers (pg_hidden3.hpp)
+//   pg_sig3.hip          k_sig3: the same for three hidden sigmoid layers (pg_sig3.hpp, on pg_hidden3.hpp's layout)
 //   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate (pg_relu2_bound.h, its block layout) with a block per
 //                        game (widths up to 128)
 //   pg_sig2_block.hip    k_sig2_block: k_sig2's certificate (pg_sig2_bound.h, its block layout) on the same layout;
@@ -235,6 +236,11 @@ int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hi
 int32_t relu3_scope(const pg_eval_args &a);
 int32_t launch_relu3(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
+// [6, 2..32, 2..32, 2..32, 2..4] sigmoid networks with bias on k_sig3 (pg_sig3.hip, pg_sig3.hpp): k_sig2's
+// certificate and cascade on k_relu3's layout; no horizon, no hard-case log
+int32_t sig3_scope(const pg_eval_args &a);
+int32_t launch_sig3(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
+
 // [6, 2..128, 2..128, 2..4] ReLU networks with bias on k_relu2_block (pg_relu2_block.hip): k_relu2's
 // certificate with a 256-thread block per game; certified precision, no workspace beyond the base, no
 // horizon, no hard-case log, no modifier bits
@@ -256,5 +262,6 @@ void relu_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t
 void relu2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 void sig2_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 void relu3_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
+void sig3_solo_game(int LN, int O, bool f64, bool advance, int grid, hipStream_t s, const EvalParams &p);
 
 }  // namespace pg

@@ -3,7 +3,10 @@
 // (activation_function = ReLU, numpy_nn.py:6-9, 26) held by a half-group of LN
 // lanes, its decision and its f64 re-decision in numpy's order: k_relu2's idiom
 // (pg_hidden2.hpp) one layer deeper.  The bound's arithmetic and its derivation
-// are in pg_relu3_bound.h (it also compiles for the host).
+// are in pg_relu3_bound.h (it also compiles for the host).  hidden3_z32 and
+// hidden3_f64_half are templates on the activation (ACT, a pg_activation, as
+// pg_hidden2.hpp's are): k_sig3 (pg_sig3.hpp) runs them with the sigmoid on this
+// layout, under a load and a bound of its own.
 //
 // Lane hl of a half-group holds layer-1 units 2 hl, 2 hl + 1 (7 weights each),
 // layer-2 units 2 hl, 2 hl + 1 (a whole row of W2 each: 2 LN weights and the
@@ -195,9 +198,10 @@ __device__ __forceinline__ void hidden3_load(Hidden3Net<LN, U, O> &n, const WT *
 }
 
 // The f32 output pre-activations z^ on the doubled-centroid features k, with
-// the chain lengths pg_relu3_bound.h bounds; every lane of the half-group gets
+// the chain lengths pg_relu3_bound.h and pg_sig3_bound.h bound (under the
+// sigmoid a padding unit's activation is 0.5, met by zero weights only); every lane of the half-group gets
 // the bitwise-identical values (group_sum).
-template <int LN, int U, int O>
+template <int ACT, int LN, int U, int O>
 __device__ __forceinline__ void hidden3_z32(const Hidden3Net<LN, U, O> &n, const int k[6], float *row1, float *row2,
                                             int hl, float z[O]) {
   static_assert(U == 2, "the vector stores below");
@@ -209,7 +213,7 @@ __device__ __forceinline__ void hidden3_z32(const Hidden3Net<LN, U, O> &n, const
     float a = n.w1[u][6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) a = fmaf(n.w1[u][i], x[i], a);
-    h1[u] = fmaxf(a, 0.f);
+    h1[u] = hidden2_act32<ACT>(a);
   }
   wave_lds_sync();  // both rows' readers of the frame before are done
   *(float2 *)(row1 + hl * U) = make_float2(h1[0], h1[1]);
@@ -228,7 +232,7 @@ __device__ __forceinline__ void hidden3_z32(const Hidden3Net<LN, U, O> &n, const
       a2[v] = fmaf(n.w2[v][j + 3], h.w, a2[v]);
     }
   }
-  *(float2 *)(row2 + hl * U) = make_float2(fmaxf(a2[0], 0.f), fmaxf(a2[1], 0.f));
+  *(float2 *)(row2 + hl * U) = make_float2(hidden2_act32<ACT>(a2[0]), hidden2_act32<ACT>(a2[1]));
   wave_lds_sync();
   float a3[U];
 #pragma unroll
@@ -249,7 +253,7 @@ __device__ __forceinline__ void hidden3_z32(const Hidden3Net<LN, U, O> &n, const
   for (int o = 0; o < O; ++o) acc[o] = 0.f;
 #pragma unroll
   for (int v = 0; v < U; ++v) {
-    const float h3 = fmaxf(a3[v], 0.f);
+    const float h3 = hidden2_act32<ACT>(a3[v]);
 #pragma unroll
     for (int o = 0; o < O; ++o) acc[o] = fmaf(n.w4[v][o], h3, acc[o]);
   }
@@ -262,7 +266,7 @@ __device__ __forceinline__ void hidden3_z32(const Hidden3Net<LN, U, O> &n, const
 // order, blas_dot over [inputs..., 1] per unit): each layer's units strided
 // over the lanes into LDS, lane o < O sums output o, every lane takes the
 // argmax.  d: the half-group's Hidden3Lds::d.
-template <int LN, int U, int O, typename WT>
+template <int ACT, int LN, int U, int O, typename WT>
 __device__ PG_SLOW_INLINE int hidden3_f64_half(const WT *__restrict__ g, int H1, int H2, int H3, const int k[6],
                                                double *d, int hl) {
   static_assert(O <= LN, "lane o sums output o");
@@ -278,7 +282,7 @@ __device__ PG_SLOW_INLINE int hidden3_f64_half(const WT *__restrict__ g, int H1,
     const WT *row = g + (long)j * 7;
     const double z = blas_dot([&](int i) { return (double)row[i]; }, [&](int i) { return i < 6 ? x[i] : 1.0; }, 7,
                               blas_kind(j, H1));
-    d1[j] = relu_f64(z);
+    d1[j] = hidden2_act64<ACT>(z);
   }
   wave_lds_sync();
   const WT *w2 = g + (long)H1 * 7;
@@ -287,7 +291,7 @@ __device__ PG_SLOW_INLINE int hidden3_f64_half(const WT *__restrict__ g, int H1,
     const WT *row = w2 + (long)j * (H1 + 1);
     const double z = blas_dot([&](int i) { return (double)row[i]; }, [&](int i) { return i < H1c ? d1[i] : 1.0; },
                               H1c + 1, blas_kind(j, H2));
-    d2[j] = relu_f64(z);
+    d2[j] = hidden2_act64<ACT>(z);
   }
   wave_lds_sync();
   const WT *w3 = w2 + (long)H2 * (H1 + 1);
@@ -296,14 +300,14 @@ __device__ PG_SLOW_INLINE int hidden3_f64_half(const WT *__restrict__ g, int H1,
     const WT *row = w3 + (long)j * (H2 + 1);
     const double z = blas_dot([&](int i) { return (double)row[i]; }, [&](int i) { return i < H2c ? d2[i] : 1.0; },
                               H2c + 1, blas_kind(j, H3));
-    d3[j] = relu_f64(z);
+    d3[j] = hidden2_act64<ACT>(z);
   }
   wave_lds_sync();
   if (hl < O) {
     const WT *row = w3 + (long)H3 * (H2 + 1) + (long)hl * (H3 + 1);
     const double z = blas_dot([&](int i) { return (double)row[i]; }, [&](int i) { return i < H3c ? d3[i] : 1.0; },
                               H3c + 1, blas_kind(hl, O));
-    out[hl] = relu_f64(z);
+    out[hl] = hidden2_act64<ACT>(z);
   }
   wave_lds_sync();
   int best = 0;  // np.argmax: the first NaN if any, else the first maximum
@@ -334,11 +338,11 @@ struct Relu3Policy {
   // that one index), else the f64 forward (stage 1)
   static __device__ __forceinline__ int decide(const Net &n, const WT *__restrict__ g, const Dims &dims, const int k[6],
                                                bool live, Lds &lds, int hl, float z[O], int &stage) {
-    hidden3_z32<LN, U, O>(n, k, lds.h1, lds.h2, hl, z);
+    hidden3_z32<PG_ACT_RELU, LN, U, O>(n, k, lds.h1, lds.h2, hl, z);
     int idx = half_broadcast<LN>(relu_certify<O>(z, n.e));
     const bool need = live && idx < 0;
     stage = need ? 1 : 0;
-    if (PG_ANY(need) && need) idx = hidden3_f64_half<LN, U, O, WT>(g, dims.H1, dims.H2, dims.H3, k, lds.d, hl);
+    if (PG_ANY(need) && need) idx = hidden3_f64_half<PG_ACT_RELU, LN, U, O, WT>(g, dims.H1, dims.H2, dims.H3, k, lds.d, hl);
     return idx < 0 ? 0 : idx;
   }
 };

@@ -378,7 +378,7 @@ static size_t split_records_bytes(const pg_eval_args *a) {
 // on SPLIT's in split_solo_scope (the bit reaches SPLIT through PG_KERNEL_AUTO only: check_modifier_bits)
 static int modifiers_in_effect(int kernel, const pg_eval_args &a, bool advance, bool solo) {
   const bool cert = kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2 ||
-                    kernel == PG_KERNEL_RELU3;
+                    kernel == PG_KERNEL_RELU3 || kernel == PG_KERNEL_SIG3;
   int bits = 0;
   if (advance && cert && !a.trace) bits |= PG_KERNEL_ADVANCE;
   if (solo && (cert || (kernel == PG_KERNEL_SPLIT && split_solo_scope(a)))) bits |= PG_KERNEL_SOLO;
@@ -435,7 +435,8 @@ static int32_t check_eval_ranges(const pg_eval_args *a) {
 // (SPLIT takes the solo bit through AUTO only: the refusal of an explicit SPLIT | SOLO is kept for now)
 static bool takes_modifier_bits(int kernel) {
   return kernel == PG_KERNEL_AUTO || kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2 ||
-         kernel == PG_KERNEL_RELU3;  // (RELU3 joined after the refusals' messages below were recorded)
+         kernel == PG_KERNEL_RELU3 || kernel == PG_KERNEL_SIG3;  // (RELU3 and SIG3 joined after the refusals' messages
+                                                                 // below were recorded)
 }
 
 static int32_t check_modifier_bits(int kernel, bool advance, bool solo) {
@@ -452,7 +453,7 @@ static int32_t check_modifier_bits(int kernel, bool advance, bool solo) {
 
 // Scope (pg_eval.hpp: each family states its own, activation first).  When a
 // kernel is asked is today's order of refusals, an asymmetry that is kept:
-// RELU2, RELU_WIDE, SIG2, RELU2_BLOCK and SIG2_BLOCK are refused out of scope on entry, even
+// RELU2, RELU_WIDE, SIG2, RELU2_BLOCK, SIG2_BLOCK, RELU3 and SIG3 are refused out of scope on entry, even
 // for an empty launch (scope_on_entry); RELU, SPLIT and WIDE only after the
 // n_genomes == 0 return -- for a network of the other activation before the
 // workspace check (scope_of_activation), for the rest at the launch (launch_games).
@@ -463,6 +464,7 @@ static int32_t scope_on_entry(const pg_eval_args &a) {
   if (a.kernel == PG_KERNEL_RELU2_BLOCK) return relu2_block_scope(a);
   if (a.kernel == PG_KERNEL_SIG2_BLOCK) return sig2_block_scope(a);
   if (a.kernel == PG_KERNEL_RELU3) return relu3_scope(a);
+  if (a.kernel == PG_KERNEL_SIG3) return sig3_scope(a);
   return PG_OK;
 }
 
@@ -581,6 +583,8 @@ static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bo
       return launch_sig2_block(p, dtype, s);
     case PG_KERNEL_RELU3:
       return launch_relu3(p, dtype, advance, solo, s);
+    case PG_KERNEL_SIG3:
+      return launch_sig3(p, dtype, advance, solo, s);
     case PG_KERNEL_GENERAL:
       return launch_general(p, dtype, s);
     default:

@@ -34,7 +34,8 @@ PG_KERNEL_SIG2 = 9
 PG_KERNEL_RELU2_BLOCK = 10  # k_relu2_block: [6, 2..128, 2..128, 2..4] ReLU networks, a block per game; takes no modifier bit
 PG_KERNEL_SIG2_BLOCK = 11  # k_sig2_block: [6, 2..128, 2..128, 2..4] sigmoid networks, a block per game; takes no modifier bit
 PG_KERNEL_RELU3 = 12  # k_relu3: [6, 2..32, 2..32, 2..32, 2..4] ReLU networks (three hidden layers); takes both modifier bits
-PG_KERNEL_ADVANCE = 0x100  # modifier bit of pg_eval_args.kernel: closed-form frame advance on RELU, RELU2, SIG2, RELU3
+PG_KERNEL_SIG3 = 13  # k_sig3: [6, 2..32, 2..32, 2..32, 2..4] sigmoid networks (three hidden layers); takes both modifier bits
+PG_KERNEL_ADVANCE = 0x100  # modifier bit of pg_eval_args.kernel: closed-form frame advance on RELU, RELU2, SIG2, RELU3, SIG3
 PG_KERNEL_SOLO = 0x800  # modifier bit of pg_eval_args.kernel: scripted-opponent games on half a lane group (the same three,
 #                         and through AUTO k_service's [6, 33..64, O] layout: pg_eval_resolve tells where it applies)
 PG_STATE_FIELDS = 16
@@ -224,6 +225,7 @@ SIGNATURES = {
     "pg_sig2_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_relu2_block_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_relu3_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
+    "pg_sig3_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_sig2_block_decide": (ctypes.c_int32, [ctypes.POINTER(PgReluDecideArgs), _vp]),
     "pg_physics_reset": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp, _vp]),
     "pg_physics_step": (ctypes.c_int32, [_vp, ctypes.c_int32, _vp, _vp]),

@@ -32,6 +32,7 @@ UNITS = [("pong_ga", "pong_ga.hip", []), ("pg_general", "pg_general.hip", []), (
          ("pg_sig2", "pg_sig2.hip", []), ("pg_relu_solo", "pg_relu.hip", ["-DPG_SOLO_UNIT"]),
          ("pg_relu2_solo", "pg_relu2.hip", ["-DPG_SOLO_UNIT"]), ("pg_sig2_solo", "pg_sig2.hip", ["-DPG_SOLO_UNIT"]),
          ("pg_relu3", "pg_relu3.hip", []), ("pg_relu3_solo", "pg_relu3.hip", ["-DPG_SOLO_UNIT"]),
+         ("pg_sig3", "pg_sig3.hip", []), ("pg_sig3_solo", "pg_sig3.hip", ["-DPG_SOLO_UNIT"]),
          ("pg_service_solo", "pg_service_solo.hip", []),
          ("pg_service_solo_o3", "pg_service_solo.hip", ["-DPG_SOLO_O3"] + _ILP)] + [
     (f"pg_service_more_L{L}_{f}", "pg_service_more.hip",

@@ -26,14 +26,14 @@ ACTIVATIONS = {"sigmoid": L.PG_ACT_SIGMOID, "relu": L.PG_ACT_RELU}
 # the modifiers a kernel name may carry after "+" (kernel_code); "+solo" (PG_KERNEL_SOLO): the same
 # families play a game against a scripted opponent on half a lane group, with the same results
 MODIFIERS = {"advance": L.PG_KERNEL_ADVANCE, "solo": L.PG_KERNEL_SOLO}
-MODIFIED = ("relu", "relu2", "sig2", "auto", "relu3")  # the bases either modifier goes with
+MODIFIED = ("relu", "relu2", "sig2", "auto", "relu3", "sig3")  # the bases either modifier goes with
 # kernels chosen by name only, without modifiers: kernel_code and kernel_name consult this mapping after KERNELS
 MORE_KERNELS = {"relu2_block": L.PG_KERNEL_RELU2_BLOCK}
 # the block-per-game kernels added since (the two mappings above are pinned by their tests): the same rules
 BLOCK_KERNELS = {"sig2_block": L.PG_KERNEL_SIG2_BLOCK}
 # the certified f32 families added since (the three mappings above are pinned by their tests): chosen by
 # name only, and a base of MODIFIED
-DEEP_KERNELS = {"relu3": L.PG_KERNEL_RELU3}
+DEEP_KERNELS = {"relu3": L.PG_KERNEL_RELU3, "sig3": L.PG_KERNEL_SIG3}
 _NAMED = (KERNELS, MORE_KERNELS, BLOCK_KERNELS, DEEP_KERNELS)  # what kernel_code and kernel_name consult, in this order
 DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 
@@ -41,7 +41,7 @@ DTYPES = {torch.float32: L.PG_F32, torch.float64: L.PG_F64}
 def kernel_code(name: str) -> int:
     """pg_eval_args.kernel for a kernel name: a key of ``KERNELS`` without "+"
     , of ``MORE_KERNELS``, of ``BLOCK_KERNELS`` or of ``DEEP_KERNELS``, optionally followed by "+advance"
-    and "+solo" in either order, each at most once and only on relu, relu2, sig2, relu3 and auto
+    and "+solo" in either order, each at most once and only on relu, relu2, sig2, relu3, sig3 and auto
     (KeyError otherwise)."""
     base, *mods = str(name).split("+")
     known = {k: v for mapping in _NAMED for k, v in mapping.items()}
@@ -421,6 +421,12 @@ class Evaluator:
         k_sig2_block's decision code, [6, 2..128, 2..128, 2..4] sigmoid networks
         with bias; stages 0..3 and the bound of the block layout)."""
         return self._relu_decide("pg_sig2_block_decide", genomes, k, genome_index)
+
+    def sig3_decide(self, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor] = None):
+        """The same for the three-hidden-layer sigmoid kernel (pg_sig3_decide:
+        k_sig3's decision code, [6, 2..32, 2..32, 2..32, 2..4] sigmoid networks
+        with bias; stages 0..3 and the bound of pg_sig3_bound.h)."""
+        return self._relu_decide("pg_sig3_decide", genomes, k, genome_index)
 
     def _relu_decide(self, entry: str, genomes: torch.Tensor, k: torch.Tensor, genome_index: Optional[torch.Tensor]):
         dev = self.device

@@ -17,6 +17,8 @@ interquartile range) of >= 20 launches are reported.
         --runs relu2_block:4096 relu_wide:4096 general:4096   # k_relu2_block
     python tools/bench_relu.py --shape 6 32 32 32 3 --dtype float32 \
         --runs relu3:65536 general:65536 relu3:65536 general:65536                # k_relu3
+    python tools/bench_relu.py --shape 6 32 32 32 3 --activation sigmoid --dtype float32 \
+        --runs sig3:65536 general:65536 sig3:65536 general:65536                  # k_sig3
     python tools/bench_relu.py --shape 6 128 128 3 --activation sigmoid --dtype float32 --launches 5 \
         --runs sig2_block:4096 wide:4096 general:4096         # k_sig2_block
     python tools/bench_relu.py --shape 6 512 512 3 --dtype float32 --launches 5 \
@@ -41,8 +43,8 @@ Every run reports rally_share and serve_delay_share: counters [8] and [12] as
 shares of the episode frames (0 for a kernel that steps every frame).
 
 --activation sets the activation of the general and wide runs (default relu;
-relu, relu2, relu3, relu2_block and relu_wide runs are always ReLU, sig2, sig2_block and service runs always
-sigmoid).  --genes uniform draws U[0, 1) genes (generation 0 of a reference
+relu, relu2, relu3, relu2_block and relu_wide runs are always ReLU, sig2, sig3, sig2_block and service runs always
+sigmoid; a five-node --shape with --activation sigmoid is what sig3 and its general runs take).  --genes uniform draws U[0, 1) genes (generation 0 of a reference
 run, ga.py:85) instead of N(0, 3).
 
 relu_wide runs also report the network passes (counter [7]) and the streaming
@@ -80,13 +82,13 @@ def workload(pop, dev, seed=1234, sigma=3.0, shape=SHAPE, dtype=torch.float64, g
 
 
 KERNEL_NAMES = {"relu": "k_relu", "relu2": "k_relu2", "relu3": "k_relu3", "relu2_block": "k_relu2_block", "sig2_block": "k_sig2_block", "relu_wide": "k_wide<relu>", "general": "k_general",
-                "service": "k_service", "sig2": "k_sig2", "wide": "k_wide", "auto": "auto"}
-FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu3": "relu", "relu2_block": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid", "sig2_block": "sigmoid",
+                "service": "k_service", "sig2": "k_sig2", "sig3": "k_sig3", "wide": "k_wide", "auto": "auto"}
+FIXED_ACTIVATION = {"relu": "relu", "relu2": "relu", "relu3": "relu", "relu2_block": "relu", "relu_wide": "relu", "service": "sigmoid", "sig2": "sigmoid", "sig2_block": "sigmoid", "sig3": "sigmoid",
                     "wide": "sigmoid"}
 # the names "+advance" and "+solo" go with (pong_amd.device.kernel_code); auto runs the network of --activation on
 # what PG_KERNEL_AUTO picks and reports it as Evaluator.resolved_kernel does: "auto+solo" with --activation sigmoid
 # --shape 6 64 3 is k_service's solo instance
-MODIFIED = ("relu", "relu2", "sig2", "auto", "relu3")
+MODIFIED = ("relu", "relu2", "sig2", "auto", "relu3", "sig3")
 SCHEDULES = {"selfplay": None, "reference": [0, 1, 2, 3, 3, 3], "scripted": [0, 1, 2, 0, 0, 0]}
 
 
@@ -149,7 +151,7 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
             "rally_share": round(int(c[8]) / max(frames, 1), 6), "serve_delay_share": round(int(c[12]) / max(frames, 1), 6),
             "genes": "U[0,1)" if genes == "uniform" else "N(0,3)",
             "device": torch.cuda.get_device_name(dev)}
-    if name.startswith("sig2"):  # the cascade: forwards the f32 certificate left undecided (counter [4])
+    if name.startswith(("sig2", "sig3")):  # the cascade: forwards the f32 certificate left undecided (counter [4])
         out["stage1_failures"] = int(c[4])
         out["stage1_failure_share"] = round(int(c[4]) / max(int(c[1]), 1), 6)
     if name == "relu_wide":  # each network pass streams one network's genes once
@@ -163,8 +165,8 @@ def run(name, pop, dev, warmup, launches, shape=SHAPE, dtype=torch.float64, acti
 
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu3, relu2_block, relu_wide, sig2, sig2_block, wide, general, service, auto, "
-                   "relu+advance, relu2+advance, relu3+advance, sig2+advance, auto+advance, and relu, relu2, relu3, sig2, auto with +solo or "
+    p.add_argument("--runs", nargs="*", default=RUNS, help="kernel:population, kernel in relu, relu2, relu3, relu2_block, relu_wide, sig2, sig3, sig2_block, wide, general, service, auto, "
+                   "relu+advance, relu2+advance, relu3+advance, sig2+advance, sig3+advance, auto+advance, and relu, relu2, relu3, sig2, sig3, auto with +solo or "
                    "+advance+solo")
     p.add_argument("--schedule", default="selfplay", choices=sorted(SCHEDULES),
                    help="the games' kinds per genome: selfplay (all against the hall), reference ([0,1,2,3,3,3]) or "

@@ -1,6 +1,6 @@
 """Where the certified f32 game kernels touch scratch, by source line.
 
-Builds pg_relu.hip, pg_relu2.hip, pg_sig2.hip and pg_relu3.hip's device objects with line
+Builds pg_relu.hip, pg_relu2.hip, pg_sig2.hip, pg_relu3.hip and pg_sig3.hip's device objects with line
 tables (the product's flags plus -gline-tables-only), disassembles every game
 kernel whose name contains SUBSTRING (default "_adv": the PG_KERNEL_ADVANCE
 instances) and reports, per kernel, its scratch_* instructions by the source
@@ -23,7 +23,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "neuro-genetic-pong-self-play_amd", "csrc")
 HIPCC = "/opt/rocm/bin/hipcc"
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
-UNITS = [(u, f) for u in ("pg_relu.hip", "pg_relu2.hip", "pg_sig2.hip", "pg_relu3.hip") for f in ((), ("-DPG_SOLO_UNIT",))]
+UNITS = [(u, f) for u in ("pg_relu.hip", "pg_relu2.hip", "pg_sig2.hip", "pg_relu3.hip", "pg_sig3.hip") for f in ((), ("-DPG_SOLO_UNIT",))]
 
 
 def listing(tmp, unit, flags):
