@@ -304,12 +304,6 @@ __device__ PG_SLOW_INLINE void block_f64(const WT *__restrict__ g, int H1, int H
 }
 
 // ------------------------------------------------------------ host side ----
-// the shapes [6, 2..128, 2..128, 2..4]
-inline bool block2_shape_ok(const pg_net &n) {
-  return n.n_nodes == 4 && n.nodes[0] == 6 && n.nodes[1] >= 2 && n.nodes[1] <= kBlockH && n.nodes[2] >= 2 &&
-         n.nodes[2] <= kBlockH && n.nodes[3] >= 2 && n.nodes[3] <= 4;
-}
-
 #define PG_BLOCK_DISPATCH(KERNEL, O, f64, grid, s, p)                                         \
   do {                                                                                        \
     if (O == 2) {                                                                             \
@@ -330,20 +324,24 @@ inline int block2_grid(int n) {
   return n < cap ? n : cap;
 }
 
-// pg_*_block_decide's checks after the family's own (activation, shape, bias): the pass's parameters, or n <= 0
-// (rc: PG_OK for an empty call, else the error)
-inline bool block2_decide_args(const pg_relu_decide_args *a, CertDecideParams &p, int32_t &rc) {
-  rc = PG_OK;
-  if (a->n < 0) rc = fail(PG_ERR_INVALID, "n=%d < 0", a->n);
-  if (a->n <= 0) return false;
-  const int H1 = a->net.nodes[1], H2 = a->net.nodes[2], O = a->net.nodes[3];
-  const long G = (long)H1 * 7 + (long)H2 * (H1 + 1) + (long)O * (H2 + 1);
-  if (!a->genomes || a->genome_stride < G || !a->k || !a->index) {
-    rc = fail(PG_ERR_INVALID, "genomes/k/index NULL or genome_stride < gene count %ld", G);
-    return false;
+// What Relu2BlockFamily (pg_relu2_block.hip) and Sig2BlockFamily
+// (pg_sig2_block.hip) share of a family's description (pg_family.hpp); each
+// adds its kernel, its activation, its messages and the launches of its
+// kernels.  No modifier bits: every frame is stepped, a block plays both paddles.
+struct Block2Family {
+  static constexpr bool kModifiers = false, kScopeOnEntry = true;
+  using DecideParams = CertDecideParams;
+  // the shapes [6, 2..128, 2..128, 2..4]
+  static bool shape_ok(int n_nodes, const int32_t *nodes) {
+    return n_nodes == 4 && nodes[0] == 6 && nodes[1] >= 2 && nodes[1] <= kBlockH && nodes[2] >= 2 &&
+           nodes[2] <= kBlockH && nodes[3] >= 2 && nodes[3] <= 4;
   }
-  p = cert_decide_params(a, H1, H2);
-  return true;
-}
+  static long genes(const int32_t *nd) { return (long)nd[1] * 7 + (long)nd[2] * (nd[1] + 1) + (long)nd[3] * (nd[2] + 1); }
+  static int game_grid(const EvalParams &p) { return block2_grid(p.total); }
+  static int decide_grid(const pg_relu_decide_args *a) { return block2_grid(a->n); }
+  static DecideParams decide_params(const pg_relu_decide_args *a) {
+    return cert_decide_params(a, a->net.nodes[1], a->net.nodes[2]);
+  }
+};
 
 }  // namespace pg

@@ -10,8 +10,10 @@
 //   pg_service_solo.hip  k_service's solo instances (PG_KERNEL_SOLO on the bench layout)
 //   pg_general.hip       the f64 path: k_general, pg_forward with k_forward_general
 //   pg_wide.hip          k_wide: wide two-hidden-layer networks, weights streamed
-//   pg_relu.hip, pg_relu2.hip, pg_sig2.hip   the certified f32 families
-//   pg_relu3.hip         k_relu3: the certified f32 family for three hidden ReLU layers (pg_hidden3.hpp)
+//   the certified f32 families, seven units on pg_certgame.hpp (device) and pg_family.hpp (host):
+//   pg_relu.hip          k_relu: one hidden ReLU layer (pg_relu.hpp)
+//   pg_relu2.hip, pg_sig2.hip   k_relu2, k_sig2: two hidden ReLU / sigmoid layers (pg_hidden2.hpp)
+//   pg_relu3.hip         k_relu3: three hidden ReLU layers (pg_hidden3.hpp)
 //   pg_sig3.hip          k_sig3: the same for three hidden sigmoid layers (pg_sig3.hpp, on pg_hidden3.hpp's layout)
 //   pg_relu2_block.hip   k_relu2_block: k_relu2's certificate (pg_relu2_bound.h, its block layout) with a block per
 //                        game (widths up to 128)
@@ -71,7 +73,7 @@ struct EvalParams {
   const int32_t *wide_probe_k;
   int32_t *wide_probe_index;  // out [n_genomes] np.argmax
   double *wide_probe_act;     // optional out [n_genomes, nodes[3]]
-  int activation;             // pg_net.activation (k_general, k_relu, k_relu2; launch_wide picks k_wide's instance by it)
+  int activation;             // pg_net.activation (k_general reads it; launch_wide picks k_wide's instance by it)
 };
 
 // Genome blocks / games this launch plays (pg_eval_args.n_active).  Made
@@ -174,12 +176,13 @@ struct DecideParams {
 int32_t launch_decide(const DecideParams &p, int L, int O, bool f64, size_t lds, hipStream_t s);
 
 // ------------------------------------------------- the kernel families ----
-// Each family's unit exports its scope and its launch.  X_scope(a) is the
-// refusal, in the family's words, of a network or of arguments that the kernel
-// does not evaluate (activation first, then shape, bias, precision, horizon,
-// hard-case log, as far as the family has a rule of its own), or PG_OK.  It is
-// the only place that states them: the launches take what pg_eval_population
-// let through.  a.kernel is the pg_kernel alone, without modifier bits.
+// Each family's unit exports its scope and its launch (the certified f32
+// families: as a FamilyDesc).  A scope is the refusal, in the family's words, of
+// a network or of arguments that the kernel does not evaluate (activation
+// first, then shape, bias, precision, horizon, hard-case log, as far as the
+// family has a rule of its own), or PG_OK.  It is the only place that states
+// them: the launches take what pg_eval_population let through.  a.kernel is
+// the pg_kernel alone, without modifier bits.
 
 // the f64 kernel for any NETWORK_SHAPE (k_general, pg_general.hip)
 int32_t launch_general(const EvalParams &p, int dtype, hipStream_t s);
@@ -217,44 +220,35 @@ size_t wide_workspace_bytes(const pg_eval_args *a);
 int32_t wide_scope(const pg_eval_args &a, bool relu);
 int32_t launch_wide(const EvalParams &p, int dtype, void *scratch, hipStream_t s);
 
-// [6, H <= 256, 2..4] ReLU networks with bias on k_relu (pg_relu.hip; certified
-// precision, no workspace beyond the base)
+// The certified f32 families: certified precision, networks with bias, no
+// workspace beyond the base.  Each unit states its family's host side once, as
+// a description for pg_family.hpp's templates, and exports this descriptor of
+// it; pong_ga.hip looks a pg_kernel up in one table of the seven.  (Exported
+// as a host function that returns the constant: a const object of namespace
+// scope would be emitted into the unit's code object as well.)
+struct FamilyDesc {
+  int kernel;      // its pg_kernel
+  bool modifiers;  // it takes PG_KERNEL_ADVANCE and PG_KERNEL_SOLO (it has k_*_adv and k_*_solo instances)
+  bool scope_on_entry;  // scope is asked on pg_eval_population's entry, even for an empty launch; else at the launch
+  int32_t (*scope)(const pg_eval_args &a);
+  // advance: the k_*_adv instances, unless the launch is traced; solo: the k_*_solo instances, traced or not
+  int32_t (*launch)(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
+};
+FamilyDesc relu_family();   // k_relu, [6, 1..256, 2..4] ReLU networks (pg_relu.hip)
+FamilyDesc relu2_family();  // k_relu2, [6, 2..64, 2..64, 2..4] ReLU networks (pg_relu2.hip, pg_hidden2.hpp)
+FamilyDesc sig2_family();   // k_sig2, the same shapes of sigmoid networks (pg_sig2.hip, pg_hidden2.hpp); like
+                            // every sigmoid family no horizon, no hard-case log
+// k_relu2_block and k_sig2_block: k_relu2's and k_sig2's certificates with a 256-thread block per game,
+// [6, 2..128, 2..128, 2..4] (pg_relu2_block.hip, pg_sig2_block.hip, pg_block2.hpp); no horizon, no hard-case
+// log, no modifier bits
+FamilyDesc relu2_block_family(), sig2_block_family();
+// k_relu3 and k_sig3: the same for three hidden layers, [6, 2..32, 2..32, 2..32, 2..4] (pg_relu3.hip on
+// pg_hidden3.hpp; pg_sig3.hip on pg_sig3.hpp: k_sig2's certificate and cascade on k_relu3's layout)
+FamilyDesc relu3_family(), sig3_family();
+
+// AUTO's choice among them for a ReLU network (resolve_kernel): the families' shapes, with bias
 bool relu_shape_ok(const pg_net &n);
-int32_t relu_scope(const pg_eval_args &a);
-// advance (PG_KERNEL_ADVANCE): the k_*_adv instances, unless the launch is traced;
-// solo (PG_KERNEL_SOLO): the k_*_solo instances, traced or not
-int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
-
-// [6, 2..64, 2..64, 2..4] ReLU networks with bias on k_relu2 (pg_relu2.hip; the
-// host side it shares with k_sig2 is pg_hidden2.hpp's): the same for two hidden layers
 bool relu2_shape_ok(const pg_net &n);
-int32_t relu2_scope(const pg_eval_args &a);
-int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
-
-// [6, 2..32, 2..32, 2..32, 2..4] ReLU networks with bias on k_relu3 (pg_relu3.hip, pg_hidden3.hpp): the
-// same for three hidden layers
-int32_t relu3_scope(const pg_eval_args &a);
-int32_t launch_relu3(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
-
-// [6, 2..32, 2..32, 2..32, 2..4] sigmoid networks with bias on k_sig3 (pg_sig3.hip, pg_sig3.hpp): k_sig2's
-// certificate and cascade on k_relu3's layout; no horizon, no hard-case log
-int32_t sig3_scope(const pg_eval_args &a);
-int32_t launch_sig3(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
-
-// [6, 2..128, 2..128, 2..4] ReLU networks with bias on k_relu2_block (pg_relu2_block.hip): k_relu2's
-// certificate with a 256-thread block per game; certified precision, no workspace beyond the base, no
-// horizon, no hard-case log, no modifier bits
-int32_t relu2_block_scope(const pg_eval_args &a);
-int32_t launch_relu2_block(const EvalParams &p, int dtype, hipStream_t s);
-
-// [6, 2..128, 2..128, 2..4] sigmoid networks with bias on k_sig2_block (pg_sig2_block.hip): k_sig2's
-// certificate and cascade on k_relu2_block's layout; the same scope otherwise
-int32_t sig2_block_scope(const pg_eval_args &a);
-int32_t launch_sig2_block(const EvalParams &p, int dtype, hipStream_t s);
-
-// [6, 2..64, 2..64, 2..4] sigmoid networks with bias on k_sig2 (pg_sig2.hip, pg_hidden2.hpp)
-int32_t sig2_scope(const pg_eval_args &a);
-int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s);
 
 // the launches of the k_*_solo / k_*_adv_solo instances (PG_KERNEL_SOLO): each
 // family's source compiled again as a unit of its own (-DPG_SOLO_UNIT)

@@ -420,9 +420,6 @@ struct Sig2Policy {
 };
 
 // ------------------------------------------------------------ host side ----
-// A family F (Relu2Family in pg_relu2.hip, Sig2Family in pg_sig2.hip) supplies
-// kActivation, its refusals' messages and the launches of its kernels.
-
 // the instances: LN = hidden2_lanes(H1, H2) lanes per network, hidden2_units(LN) units of each layer per lane
 #define PG_HIDDEN2_DISPATCH(KERNEL, LN, O, f64, grid, s, p)                                                    \
   do {                                                                                                         \
@@ -431,63 +428,27 @@ struct Sig2Policy {
     else PG_CERT_DISPATCH(KERNEL, 32, (hidden2_units(32), hidden2_units(32)), O, f64, grid, s, p);             \
   } while (0)
 
-// the shapes [6, 2..64, 2..64, 2..4] (the bias is checked apart: k_sig2's refusal of it has its own message)
-inline bool hidden2_shape_ok(int n_nodes, const int32_t *nodes) {
-  return n_nodes == 4 && nodes[0] == 6 && nodes[1] >= 2 && nodes[1] <= kHidden2MaxH && nodes[2] >= 2 &&
-         nodes[2] <= kHidden2MaxH && nodes[3] >= 2 && nodes[3] <= 4;
-}
-
-inline long hidden2_genes(int H1, int H2, int O) { return (long)H1 * 7 + (long)H2 * (H1 + 1) + (long)O * (H2 + 1); }
-
 static_assert(4 * hidden2_units(4) >= 16 && 16 * hidden2_units(16) >= 32 && 32 * hidden2_units(32) >= kHidden2MaxH,
               "hidden2_lanes' thresholds: a layout for every H1, H2 in scope");
 
-// The family's scope (pg_eval.hpp), in its words.  Only the sigmoid family has
-// rules of its own for a horizon and a hard-case log: pg_eval_population
-// refuses both for every ReLU network, after its empty-launch return.
-template <class F>
-int32_t hidden2_scope(const pg_eval_args &a) {
-  if (a.net.activation != F::kActivation) return F::bad_activation();
-  if (!hidden2_shape_ok(a.net.n_nodes, a.net.nodes)) return F::bad_shape();
-  if (!a.net.bias) return F::no_bias();
-  if (a.precision == PG_PREC_F64) return F::no_f64();
-  if constexpr (F::kActivation == PG_ACT_SIGMOID) {
-    if (a.horizon > 0) return F::no_horizon();
-    if (a.hard_log) return F::no_hard_log();
+// What Relu2Family (pg_relu2.hip) and Sig2Family (pg_sig2.hip) share of a
+// family's description (pg_family.hpp); each adds its kernel, its activation,
+// its messages and the launches of its kernels.
+struct Hidden2Family {
+  static constexpr bool kModifiers = true, kScopeOnEntry = true;
+  using DecideParams = CertDecideParams;
+  // the shapes [6, 2..64, 2..64, 2..4]
+  static bool shape_ok(int n_nodes, const int32_t *nodes) {
+    return n_nodes == 4 && nodes[0] == 6 && nodes[1] >= 2 && nodes[1] <= kHidden2MaxH && nodes[2] >= 2 &&
+           nodes[2] <= kHidden2MaxH && nodes[3] >= 2 && nodes[3] <= 4;
   }
-  return PG_OK;
-}
-
-// p: a network in hidden2_scope, row strides of at least its gene count (pg_eval_population)
-template <class F>
-int32_t hidden2_launch(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
-  const int LN = hidden2_lanes(p.nodes[1], p.nodes[2]), O = p.nodes[3];
-  const int grid = cert_game_grid(p, LN);
-  if (grid <= 0) return PG_OK;
-  // a traced launch records every frame: it runs with the advance off
-  F::game(LN, O, dtype == PG_F64, advance && !p.trace, solo, grid, s, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
-}
-
-template <class F>
-int32_t hidden2_decide(const pg_relu_decide_args *a, void *stream) {
-  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
-  if (a->net.dtype != PG_F32 && a->net.dtype != PG_F64) return fail(PG_ERR_INVALID, "net.dtype=%d", a->net.dtype);
-  if (a->net.activation != F::kActivation) return F::decide_bad_activation(a->net.activation);
-  if (!hidden2_shape_ok(a->net.n_nodes, a->net.nodes)) return F::decide_bad_shape();
-  if (!a->net.bias) return F::decide_no_bias();
-  if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);
-  if (a->n == 0) return PG_OK;
-  const int H1 = a->net.nodes[1], H2 = a->net.nodes[2], O = a->net.nodes[3];
-  const long G = hidden2_genes(H1, H2, O);
-  if (!a->genomes || a->genome_stride < G || !a->k || !a->index)
-    return fail(PG_ERR_INVALID, "genomes/k/index NULL or genome_stride < gene count %ld", G);
-  const int LN = hidden2_lanes(H1, H2);
-  const CertDecideParams p = cert_decide_params(a, H1, H2);
-  F::decide(LN, O, a->net.dtype == PG_F64, cert_decide_grid(a->n, LN), (hipStream_t)stream, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
-}
+  static long genes(const int32_t *nd) { return (long)nd[1] * 7 + (long)nd[2] * (nd[1] + 1) + (long)nd[3] * (nd[2] + 1); }
+  static int lanes(const int32_t *nd) { return hidden2_lanes(nd[1], nd[2]); }
+  static int game_grid(const EvalParams &p) { return cert_game_grid(p, lanes(p.nodes)); }
+  static int decide_grid(const pg_relu_decide_args *a) { return cert_decide_grid(a->n, lanes(a->net.nodes)); }
+  static DecideParams decide_params(const pg_relu_decide_args *a) {
+    return cert_decide_params(a, a->net.nodes[1], a->net.nodes[2]);
+  }
+};
 
 }  // namespace pg

@@ -358,16 +358,31 @@ struct Relu3Policy {
 static_assert(8 * kHidden3Units >= 16 && 16 * kHidden3Units >= kHidden3MaxH,
               "hidden3_lanes' thresholds: a layout for every width in scope");
 
-// the shapes [6, 2..32, 2..32, 2..32, 2..4]
-inline bool hidden3_shape_ok(int n_nodes, const int32_t *nodes) {
-  if (n_nodes != 5 || nodes[0] != 6 || nodes[4] < 2 || nodes[4] > 4) return false;
-  for (int i = 1; i <= 3; ++i)
-    if (nodes[i] < 2 || nodes[i] > kHidden3MaxH) return false;
-  return true;
-}
-
-inline long hidden3_genes(int H1, int H2, int H3, int O) {
-  return (long)H1 * 7 + (long)H2 * (H1 + 1) + (long)H3 * (H2 + 1) + (long)O * (H3 + 1);
-}
+// What Relu3Family (pg_relu3.hip) and Sig3Family (pg_sig3.hip) share of a
+// family's description (pg_family.hpp); each adds its kernel, its activation,
+// its messages and the launches of its kernels.
+struct Hidden3Family {
+  static constexpr bool kModifiers = true, kScopeOnEntry = true;
+  using DecideParams = Hidden3DecideParams;
+  // the shapes [6, 2..32, 2..32, 2..32, 2..4]
+  static bool shape_ok(int n_nodes, const int32_t *nodes) {
+    if (n_nodes != 5 || nodes[0] != 6 || nodes[4] < 2 || nodes[4] > 4) return false;
+    for (int i = 1; i <= 3; ++i)
+      if (nodes[i] < 2 || nodes[i] > kHidden3MaxH) return false;
+    return true;
+  }
+  static long genes(const int32_t *nd) {
+    return (long)nd[1] * 7 + (long)nd[2] * (nd[1] + 1) + (long)nd[3] * (nd[2] + 1) + (long)nd[4] * (nd[3] + 1);
+  }
+  static int lanes(const int32_t *nd) { return hidden3_lanes(nd[1], nd[2], nd[3]); }
+  static int game_grid(const EvalParams &p) { return cert_game_grid(p, lanes(p.nodes)); }
+  static int decide_grid(const pg_relu_decide_args *a) { return cert_decide_grid(a->n, lanes(a->net.nodes)); }
+  static DecideParams decide_params(const pg_relu_decide_args *a) {
+    DecideParams p;
+    static_cast<CertDecideParams &>(p) = cert_decide_params(a, a->net.nodes[1], a->net.nodes[2]);
+    p.H3 = a->net.nodes[3];
+    return p;
+  }
+};
 
 }  // namespace pg

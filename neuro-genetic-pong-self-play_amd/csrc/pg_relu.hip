@@ -15,8 +15,9 @@
 //                         undecided half-groups the f64 forward in numpy's order
 //                         from the genes.  Every frame is stepped.
 // The game loop and the decide pass are the certified families' shared ones
-// (pg_certgame.hpp); this file holds k_relu's policy and its host side.
-// Compiled a second time with -DPG_SOLO_UNIT (pong_amd/build.py) it holds
+// (pg_certgame.hpp); this file holds k_relu's policy, its kernels, its
+// description (pg_family.hpp), its row of the family table and its C entry
+// point.  Compiled a second time with -DPG_SOLO_UNIT (pong_amd/build.py) it holds
 // k_relu_solo and k_relu_adv_solo (PG_KERNEL_SOLO) and nothing else, so this
 // unit's kernels are what they were without them.  DESIGN.md 4.2c, 4.2g, 4.2i.
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 #include "pg_certgame.hpp"
 #include "pg_device.hpp"
 #include "pg_eval.hpp"
+#include "pg_family.hpp"
 #include "pg_relu.hpp"
 
 namespace pg {
@@ -100,63 +102,49 @@ __global__ __launch_bounds__(256) void k_relu_decide(CertDecideParams p) {
     cert_decide_pass<ReluPolicy<LN, U, O, WT>>(p, base);
 }
 
-bool relu_shape_ok(const pg_net &n) {
-  return n.n_nodes == 3 && n.nodes[0] == 6 && n.nodes[1] >= 1 && n.nodes[1] <= kReluMaxH && n.nodes[2] >= 2 &&
-         n.nodes[2] <= 4 && n.bias != 0;
-}
-
 static_assert(relu_lanes(kReluMaxH) * kReluUnits >= kReluMaxH, "a layout for every H in scope");
 
-int32_t relu_scope(const pg_eval_args &a) {
-  if (a.net.activation != PG_ACT_RELU)
-    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu kernel evaluates PG_ACT_RELU networks only");
-  if (!relu_shape_ok(a.net))
-    return fail(PG_ERR_UNSUPPORTED, "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias");
-  if (a.precision != PG_PREC_CERTIFIED) return fail(PG_ERR_UNSUPPORTED, "relu kernel is the certified-precision path");
-  return PG_OK;
-}
+// k_relu's description (pg_family.hpp).  The one family whose scope is asked at
+// the launch, not on entry (pong_ga.hip's scope_on_entry says what that keeps).
+struct ReluFamily {
+  static constexpr int kKernel = PG_KERNEL_RELU, kActivation = PG_ACT_RELU;
+  static constexpr bool kModifiers = true, kScopeOnEntry = false;
+  static constexpr const char *kName = "relu";
+  static constexpr const char *kBadActivation = "activation sigmoid: the relu kernel evaluates PG_ACT_RELU networks only";
+  static constexpr const char *kBadShape = "relu kernel needs NETWORK_SHAPE [6, H<=256, 2..4] with bias";
+  static constexpr const char *kNoBias = kBadShape;
+  static constexpr const char *kDecideBadActivation =
+      "pg_relu_decide: activation=%d, the relu kernel decides PG_ACT_RELU networks only";
+  static constexpr const char *kDecideBadShape = "pg_relu_decide: the relu kernel's shapes [6, H<=256, 2..4] with bias only";
+  static constexpr const char *kDecideNoBias = kDecideBadShape;
+  using DecideParams = CertDecideParams;
+  // the shapes [6, 1..256, 2..4]
+  static bool shape_ok(int n_nodes, const int32_t *nodes) {
+    return n_nodes == 3 && nodes[0] == 6 && nodes[1] >= 1 && nodes[1] <= kReluMaxH && nodes[2] >= 2 && nodes[2] <= 4;
+  }
+  static long genes(const int32_t *nd) { return (long)nd[1] * 7 + (long)nd[2] * (nd[1] + 1); }
+  static int lanes(const int32_t *nd) { return relu_lanes(nd[1]); }
+  static int game_grid(const EvalParams &p) { return cert_game_grid(p, lanes(p.nodes)); }
+  static int decide_grid(const pg_relu_decide_args *a) { return cert_decide_grid(a->n, lanes(a->net.nodes)); }
+  static DecideParams decide_params(const pg_relu_decide_args *a) { return cert_decide_params(a, a->net.nodes[1], 0); }
+  static void game(const EvalParams &p, bool f64, bool advance, bool solo, int grid, hipStream_t s) {
+    const int LN = lanes(p.nodes), O = p.nodes[2];
+    if (solo) relu_solo_game(LN, O, f64, advance, grid, s, p);
+    else if (advance) PG_RELU_DISPATCH(k_relu_adv, LN, O, f64, grid, s, p);
+    else PG_RELU_DISPATCH(k_relu, LN, O, f64, grid, s, p);
+  }
+  static void decide(const int32_t *nodes, bool f64, int grid, hipStream_t s, const DecideParams &p) {
+    PG_RELU_DISPATCH(k_relu_decide, lanes(nodes), nodes[2], f64, grid, s, p);
+  }
+};
 
-static long relu_genes(int H, int O) { return (long)H * 7 + (long)O * (H + 1); }
+bool relu_shape_ok(const pg_net &n) { return ReluFamily::shape_ok(n.n_nodes, n.nodes) && n.bias != 0; }
 
-// p: a network in relu_scope, row strides of at least its gene count (pg_eval_population)
-int32_t launch_relu(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
-  const int H = p.nodes[1], O = p.nodes[2];
-  const int LN = relu_lanes(H);
-  const int grid = cert_game_grid(p, LN);
-  if (grid <= 0) return PG_OK;
-  // a traced launch records every frame: it runs with the advance off
-  if (solo) relu_solo_game(LN, O, dtype == PG_F64, advance && !p.trace, grid, s, p);
-  else if (advance && !p.trace) PG_RELU_DISPATCH(k_relu_adv, LN, O, dtype == PG_F64, grid, s, p);
-  else PG_RELU_DISPATCH(k_relu, LN, O, dtype == PG_F64, grid, s, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
-}
+FamilyDesc relu_family() { return family_desc<ReluFamily>(); }
 
 }  // namespace pg
 
-using namespace pg;
-
 extern "C" int32_t pg_relu_decide(const pg_relu_decide_args *a, void *stream) {
-  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
-  if (a->net.dtype != PG_F32 && a->net.dtype != PG_F64) return fail(PG_ERR_INVALID, "net.dtype=%d", a->net.dtype);
-  if (a->net.activation != PG_ACT_RELU)
-    return fail(PG_ERR_UNSUPPORTED, "pg_relu_decide: activation=%d, the relu kernel decides PG_ACT_RELU networks only",
-                a->net.activation);
-  if (!relu_shape_ok(a->net))
-    return fail(PG_ERR_UNSUPPORTED, "pg_relu_decide: the relu kernel's shapes [6, H<=256, 2..4] with bias only");
-  if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);
-  if (a->n == 0) return PG_OK;
-  const int H = a->net.nodes[1], O = a->net.nodes[2];
-  const long G = relu_genes(H, O);
-  if (!a->genomes || a->genome_stride < G || !a->k || !a->index)
-    return fail(PG_ERR_INVALID, "genomes/k/index NULL or genome_stride < gene count %ld", G);
-  const int LN = relu_lanes(H);
-  if (LN * kReluUnits < H) return fail(PG_ERR_UNSUPPORTED, "pg_relu_decide: no layout for H=%d", H);
-  const CertDecideParams p = cert_decide_params(a, H, 0);
-  const int grid = cert_decide_grid(a->n, LN);
-  hipStream_t s = (hipStream_t)stream;
-  PG_RELU_DISPATCH(k_relu_decide, LN, O, a->net.dtype == PG_F64, grid, s, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
+  return pg::family_decide<pg::ReluFamily>(a, stream);
 }
 #endif  // PG_SOLO_UNIT

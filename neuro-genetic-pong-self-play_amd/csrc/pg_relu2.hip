@@ -12,16 +12,18 @@
 //                         network's static bound (pg_relu2_bound.h), and for the
 //                         undecided half-groups the f64 forward in numpy's
 //                         order from the genes.
-// This file holds the family's kernels, its messages and its C entry point; the
-// host side it shares with k_sig2 is pg_hidden2.hpp's.  Compiled a second time
-// with -DPG_SOLO_UNIT (pong_amd/build.py) it holds k_relu2_solo and
-// k_relu2_adv_solo (PG_KERNEL_SOLO) and nothing else, so this unit's kernels
-// are what they were without them.  DESIGN.md 4.2d, 4.2g.
+// This file holds the family's kernels, its description (pg_family.hpp; what it
+// shares with k_sig2's is pg_hidden2.hpp's Hidden2Family), its row of the family
+// table and its C entry point.  Compiled a second time with -DPG_SOLO_UNIT
+// (pong_amd/build.py) it holds k_relu2_solo and k_relu2_adv_solo
+// (PG_KERNEL_SOLO) and nothing else, so this unit's kernels are what they were
+// without them.  DESIGN.md 4.2d, 4.2g.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pong_ga.h"
 #include "pg_certgame.hpp"
 #include "pg_eval.hpp"
+#include "pg_family.hpp"
 #include "pg_hidden2.hpp"
 
 namespace pg {
@@ -69,45 +71,35 @@ __global__ __launch_bounds__(256) void k_relu2_decide(CertDecideParams p) {
     cert_decide_pass<Relu2Policy<LN, U1, U2, O, WT>>(p, base);
 }
 
-bool relu2_shape_ok(const pg_net &n) { return hidden2_shape_ok(n.n_nodes, n.nodes) && n.bias != 0; }
-
-struct Relu2Family {
-  static constexpr int kActivation = PG_ACT_RELU;
-  static int32_t bad_activation() {
-    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu2 kernel evaluates PG_ACT_RELU networks only");
-  }
-  static int32_t bad_shape() {
-    return fail(PG_ERR_UNSUPPORTED, "relu2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4] with bias");
-  }
-  static int32_t no_bias() { return bad_shape(); }
-  static int32_t no_f64() { return fail(PG_ERR_UNSUPPORTED, "relu2 kernel is the certified-precision path"); }
-  static int32_t decide_bad_activation(int activation) {
-    return fail(PG_ERR_UNSUPPORTED, "pg_relu2_decide: activation=%d, the relu2 kernel decides PG_ACT_RELU networks only",
-                activation);
-  }
-  static int32_t decide_bad_shape() {
-    return fail(PG_ERR_UNSUPPORTED, "pg_relu2_decide: the relu2 kernel's shapes [6, 2..64, 2..64, 2..4] with bias only");
-  }
-  static int32_t decide_no_bias() { return decide_bad_shape(); }
-  static void game(int LN, int O, bool f64, bool advance, bool solo, int grid, hipStream_t s, const EvalParams &p) {
+struct Relu2Family : Hidden2Family {
+  static constexpr int kKernel = PG_KERNEL_RELU2, kActivation = PG_ACT_RELU;
+  static constexpr const char *kName = "relu2";
+  static constexpr const char *kBadActivation = "activation sigmoid: the relu2 kernel evaluates PG_ACT_RELU networks only";
+  static constexpr const char *kBadShape = "relu2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4] with bias";
+  static constexpr const char *kNoBias = kBadShape;
+  static constexpr const char *kDecideBadActivation =
+      "pg_relu2_decide: activation=%d, the relu2 kernel decides PG_ACT_RELU networks only";
+  static constexpr const char *kDecideBadShape =
+      "pg_relu2_decide: the relu2 kernel's shapes [6, 2..64, 2..64, 2..4] with bias only";
+  static constexpr const char *kDecideNoBias = kDecideBadShape;
+  static void game(const EvalParams &p, bool f64, bool advance, bool solo, int grid, hipStream_t s) {
+    const int LN = lanes(p.nodes), O = p.nodes[3];
     if (solo) relu2_solo_game(LN, O, f64, advance, grid, s, p);
     else if (advance) PG_HIDDEN2_DISPATCH(k_relu2_adv, LN, O, f64, grid, s, p);
     else PG_HIDDEN2_DISPATCH(k_relu2, LN, O, f64, grid, s, p);
   }
-  static void decide(int LN, int O, bool f64, int grid, hipStream_t s, const CertDecideParams &p) {
-    PG_HIDDEN2_DISPATCH(k_relu2_decide, LN, O, f64, grid, s, p);
+  static void decide(const int32_t *nodes, bool f64, int grid, hipStream_t s, const DecideParams &p) {
+    PG_HIDDEN2_DISPATCH(k_relu2_decide, lanes(nodes), nodes[3], f64, grid, s, p);
   }
 };
 
-int32_t relu2_scope(const pg_eval_args &a) { return hidden2_scope<Relu2Family>(a); }
+bool relu2_shape_ok(const pg_net &n) { return Relu2Family::shape_ok(n.n_nodes, n.nodes) && n.bias != 0; }
 
-int32_t launch_relu2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
-  return hidden2_launch<Relu2Family>(p, dtype, advance, solo, s);
-}
+FamilyDesc relu2_family() { return family_desc<Relu2Family>(); }
 
 }  // namespace pg
 
 extern "C" int32_t pg_relu2_decide(const pg_relu_decide_args *a, void *stream) {
-  return pg::hidden2_decide<pg::Relu2Family>(a, stream);
+  return pg::family_decide<pg::Relu2Family>(a, stream);
 }
 #endif  // PG_SOLO_UNIT

@@ -24,6 +24,7 @@
 
 #include "../../include/pong_ga.h"
 #include "pg_block2.hpp"
+#include "pg_family.hpp"
 #include "pg_relu2_bound.h"
 
 namespace pg {
@@ -194,44 +195,33 @@ __global__ __launch_bounds__(256, 2) void k_relu2_block_decide(CertDecideParams 
 }
 
 // ------------------------------------------------------------ host side ----
-int32_t relu2_block_scope(const pg_eval_args &a) {
-  if (a.net.activation != PG_ACT_RELU)
-    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu2_block kernel evaluates PG_ACT_RELU networks only");
-  if (!block2_shape_ok(a.net) || !a.net.bias)
-    return fail(PG_ERR_UNSUPPORTED, "relu2_block kernel needs NETWORK_SHAPE [6, 2..128, 2..128, 2..4] with bias");
-  if (a.precision == PG_PREC_F64) return fail(PG_ERR_UNSUPPORTED, "relu2_block kernel is the certified-precision path");
-  if (a.horizon > 0)
-    return fail(PG_ERR_UNSUPPORTED, "relu2_block kernel plays whole episodes: no fixed-horizon mode (horizon must be 0)");
-  if (a.hard_log) return fail(PG_ERR_UNSUPPORTED, "relu2_block kernel keeps no hard-case log (hard_log must be NULL)");
-  return PG_OK;
-}
+struct Relu2BlockFamily : Block2Family {
+  static constexpr int kKernel = PG_KERNEL_RELU2_BLOCK, kActivation = PG_ACT_RELU;
+  static constexpr const char *kName = "relu2_block";
+  static constexpr const char *kBadActivation =
+      "activation sigmoid: the relu2_block kernel evaluates PG_ACT_RELU networks only";
+  static constexpr const char *kBadShape = "relu2_block kernel needs NETWORK_SHAPE [6, 2..128, 2..128, 2..4] with bias";
+  static constexpr const char *kNoBias = kBadShape;
+  static constexpr const char *kNoHorizon =
+      "relu2_block kernel plays whole episodes: no fixed-horizon mode (horizon must be 0)";
+  static constexpr const char *kNoHardLog = "relu2_block kernel keeps no hard-case log (hard_log must be NULL)";
+  static constexpr const char *kDecideBadActivation =
+      "pg_relu2_block_decide: activation=%d, the relu2_block kernel decides PG_ACT_RELU networks only";
+  static constexpr const char *kDecideBadShape =
+      "pg_relu2_block_decide: the relu2_block kernel's shapes [6, 2..128, 2..128, 2..4] with bias only";
+  static constexpr const char *kDecideNoBias = kDecideBadShape;
+  static void game(const EvalParams &p, bool f64, bool, bool, int grid, hipStream_t s) {
+    PG_BLOCK_DISPATCH(k_relu2_block, p.nodes[3], f64, grid, s, p);
+  }
+  static void decide(const int32_t *nodes, bool f64, int grid, hipStream_t s, const DecideParams &p) {
+    PG_BLOCK_DISPATCH(k_relu2_block_decide, nodes[3], f64, grid, s, p);
+  }
+};
 
-// p: a network in relu2_block_scope, row strides of at least its gene count (pg_eval_population)
-int32_t launch_relu2_block(const EvalParams &p, int dtype, hipStream_t s) {
-  const int grid = block2_grid(p.total);
-  if (grid <= 0) return PG_OK;
-  PG_BLOCK_DISPATCH(k_relu2_block, p.nodes[3], dtype == PG_F64, grid, s, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
-}
+FamilyDesc relu2_block_family() { return family_desc<Relu2BlockFamily>(); }
 
 }  // namespace pg
 
 extern "C" int32_t pg_relu2_block_decide(const pg_relu_decide_args *a, void *stream) {
-  using namespace pg;
-  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
-  if (a->net.dtype != PG_F32 && a->net.dtype != PG_F64) return fail(PG_ERR_INVALID, "net.dtype=%d", a->net.dtype);
-  if (a->net.activation != PG_ACT_RELU)
-    return fail(PG_ERR_UNSUPPORTED,
-                "pg_relu2_block_decide: activation=%d, the relu2_block kernel decides PG_ACT_RELU networks only",
-                a->net.activation);
-  if (!block2_shape_ok(a->net) || !a->net.bias)
-    return fail(PG_ERR_UNSUPPORTED,
-                "pg_relu2_block_decide: the relu2_block kernel's shapes [6, 2..128, 2..128, 2..4] with bias only");
-  CertDecideParams p;
-  int32_t rc;
-  if (!block2_decide_args(a, p, rc)) return rc;
-  PG_BLOCK_DISPATCH(k_relu2_block_decide, a->net.nodes[3], a->net.dtype == PG_F64, block2_grid(a->n), (hipStream_t)stream, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
+  return pg::family_decide<pg::Relu2BlockFamily>(a, stream);
 }

@@ -12,15 +12,17 @@
 //                         network's static bound (pg_relu3_bound.h), and for the
 //                         undecided half-groups the f64 forward in numpy's
 //                         order from the genes.
-// This file holds the family's kernels, its scope and messages and its C entry
-// point.  Compiled a second time with -DPG_SOLO_UNIT (pong_amd/build.py) it
-// holds k_relu3_solo and k_relu3_adv_solo (PG_KERNEL_SOLO) and nothing else, as
-// pg_relu2.hip does.  DESIGN.md 4.2m.
+// This file holds the family's kernels, its description (pg_family.hpp; what it
+// shares with k_sig3's is pg_hidden3.hpp's Hidden3Family), its row of the family
+// table and its C entry point.  Compiled a second time with -DPG_SOLO_UNIT
+// (pong_amd/build.py) it holds k_relu3_solo and k_relu3_adv_solo
+// (PG_KERNEL_SOLO) and nothing else, as pg_relu2.hip does.  DESIGN.md 4.2m.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pong_ga.h"
 #include "pg_certgame.hpp"
 #include "pg_eval.hpp"
+#include "pg_family.hpp"
 #include "pg_hidden3.hpp"
 
 namespace pg {
@@ -80,60 +82,33 @@ __global__ __launch_bounds__(256) void k_relu3_decide(Hidden3DecideParams p) {
     cert_decide_pass<Relu3Policy<LN, U, O, WT>>(p, base);
 }
 
-static int32_t relu3_bad_shape() {
-  return fail(PG_ERR_UNSUPPORTED, "relu3 kernel needs NETWORK_SHAPE [6, 2..32, 2..32, 2..32, 2..4] with bias");
-}
+struct Relu3Family : Hidden3Family {
+  static constexpr int kKernel = PG_KERNEL_RELU3, kActivation = PG_ACT_RELU;
+  static constexpr const char *kName = "relu3";
+  static constexpr const char *kBadActivation = "activation sigmoid: the relu3 kernel evaluates PG_ACT_RELU networks only";
+  static constexpr const char *kBadShape = "relu3 kernel needs NETWORK_SHAPE [6, 2..32, 2..32, 2..32, 2..4] with bias";
+  static constexpr const char *kNoBias = kBadShape;
+  static constexpr const char *kDecideBadActivation =
+      "pg_relu3_decide: activation=%d, the relu3 kernel decides PG_ACT_RELU networks only";
+  static constexpr const char *kDecideBadShape =
+      "pg_relu3_decide: the relu3 kernel's shapes [6, 2..32, 2..32, 2..32, 2..4] with bias only";
+  static constexpr const char *kDecideNoBias = kDecideBadShape;
+  static void game(const EvalParams &p, bool f64, bool advance, bool solo, int grid, hipStream_t s) {
+    const int LN = lanes(p.nodes), O = p.nodes[4];
+    if (solo) relu3_solo_game(LN, O, f64, advance, grid, s, p);
+    else if (advance) PG_HIDDEN3_DISPATCH(k_relu3_adv, LN, O, f64, grid, s, p);
+    else PG_HIDDEN3_DISPATCH(k_relu3, LN, O, f64, grid, s, p);
+  }
+  static void decide(const int32_t *nodes, bool f64, int grid, hipStream_t s, const DecideParams &p) {
+    PG_HIDDEN3_DISPATCH(k_relu3_decide, lanes(nodes), nodes[4], f64, grid, s, p);
+  }
+};
 
-// The family's scope (pg_eval.hpp), in its words.  A horizon and a hard-case
-// log are refused for every ReLU network by pg_eval_population, after its
-// empty-launch return.
-int32_t relu3_scope(const pg_eval_args &a) {
-  if (a.net.activation != PG_ACT_RELU)
-    return fail(PG_ERR_UNSUPPORTED, "activation sigmoid: the relu3 kernel evaluates PG_ACT_RELU networks only");
-  if (!hidden3_shape_ok(a.net.n_nodes, a.net.nodes) || !a.net.bias) return relu3_bad_shape();
-  if (a.precision == PG_PREC_F64) return fail(PG_ERR_UNSUPPORTED, "relu3 kernel is the certified-precision path");
-  return PG_OK;
-}
-
-// p: a network in relu3_scope, row strides of at least its gene count (pg_eval_population)
-int32_t launch_relu3(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
-  const int LN = hidden3_lanes(p.nodes[1], p.nodes[2], p.nodes[3]), O = p.nodes[4];
-  const int grid = cert_game_grid(p, LN);
-  if (grid <= 0) return PG_OK;
-  const bool f64 = dtype == PG_F64;
-  // a traced launch records every frame: it runs with the advance off
-  if (solo) relu3_solo_game(LN, O, f64, advance && !p.trace, grid, s, p);
-  else if (advance && !p.trace) PG_HIDDEN3_DISPATCH(k_relu3_adv, LN, O, f64, grid, s, p);
-  else PG_HIDDEN3_DISPATCH(k_relu3, LN, O, f64, grid, s, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
-}
+FamilyDesc relu3_family() { return family_desc<Relu3Family>(); }
 
 }  // namespace pg
 
 extern "C" int32_t pg_relu3_decide(const pg_relu_decide_args *a, void *stream) {
-  using namespace pg;
-  if (!a) return fail(PG_ERR_INVALID, "args is NULL");
-  if (a->net.dtype != PG_F32 && a->net.dtype != PG_F64) return fail(PG_ERR_INVALID, "net.dtype=%d", a->net.dtype);
-  if (a->net.activation != PG_ACT_RELU)
-    return fail(PG_ERR_UNSUPPORTED, "pg_relu3_decide: activation=%d, the relu3 kernel decides PG_ACT_RELU networks only",
-                a->net.activation);
-  if (!hidden3_shape_ok(a->net.n_nodes, a->net.nodes) || !a->net.bias)
-    return fail(PG_ERR_UNSUPPORTED,
-                "pg_relu3_decide: the relu3 kernel's shapes [6, 2..32, 2..32, 2..32, 2..4] with bias only");
-  if (a->n < 0) return fail(PG_ERR_INVALID, "n=%d < 0", a->n);
-  if (a->n == 0) return PG_OK;
-  const int H1 = a->net.nodes[1], H2 = a->net.nodes[2], H3 = a->net.nodes[3], O = a->net.nodes[4];
-  const long G = hidden3_genes(H1, H2, H3, O);
-  if (!a->genomes || a->genome_stride < G || !a->k || !a->index)
-    return fail(PG_ERR_INVALID, "genomes/k/index NULL or genome_stride < gene count %ld", G);
-  const int LN = hidden3_lanes(H1, H2, H3);
-  Hidden3DecideParams p;
-  static_cast<CertDecideParams &>(p) = cert_decide_params(a, H1, H2);
-  p.H3 = H3;
-  const int grid = cert_decide_grid(a->n, LN);
-  PG_HIDDEN3_DISPATCH(k_relu3_decide, LN, O, a->net.dtype == PG_F64, grid, (hipStream_t)stream, p);
-  PG_HIP(hipGetLastError());
-  return PG_OK;
+  return pg::family_decide<pg::Relu3Family>(a, stream);
 }
 #endif  // PG_SOLO_UNIT

@@ -12,16 +12,18 @@
 //                         the undecided half-groups tight_gap_move, plateau_f32
 //                         and then the f64 forward in numpy's order from the
 //                         genes.  No lane records, no workspace beyond the base.
-// This file holds the family's kernels, its messages and its C entry point; the
-// host side it shares with k_relu2 is pg_hidden2.hpp's.  Compiled a second time
-// with -DPG_SOLO_UNIT (pong_amd/build.py) it holds k_sig2_solo and
-// k_sig2_adv_solo (PG_KERNEL_SOLO) and nothing else, so this unit's kernels
-// are what they were without them.  DESIGN.md 4.2f, 4.2g.
+// This file holds the family's kernels, its description (pg_family.hpp; what it
+// shares with k_relu2's is pg_hidden2.hpp's Hidden2Family), its row of the family
+// table and its C entry point.  Compiled a second time with -DPG_SOLO_UNIT
+// (pong_amd/build.py) it holds k_sig2_solo and k_sig2_adv_solo (PG_KERNEL_SOLO)
+// and nothing else, so this unit's kernels are what they were without them
+// (DESIGN.md 4.2i).  DESIGN.md 4.2f, 4.2g.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pong_ga.h"
 #include "pg_certgame.hpp"
 #include "pg_eval.hpp"
+#include "pg_family.hpp"
 #include "pg_hidden2.hpp"
 
 namespace pg {
@@ -69,51 +71,35 @@ __global__ __launch_bounds__(256) void k_sig2_decide(CertDecideParams p) {
     cert_decide_pass<Sig2Policy<LN, U1, U2, O, WT>>(p, base);
 }
 
-struct Sig2Family {
-  static constexpr int kActivation = PG_ACT_SIGMOID;
-  static int32_t bad_activation() {
-    return fail(PG_ERR_UNSUPPORTED, "activation relu: the sig2 kernel evaluates sigmoid networks only (use RELU2)");
-  }
-  static int32_t bad_shape() {
-    return fail(PG_ERR_UNSUPPORTED, "sig2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4]");
-  }
-  static int32_t no_bias() { return fail(PG_ERR_UNSUPPORTED, "sig2 kernel needs a network with bias"); }
-  static int32_t no_f64() { return fail(PG_ERR_UNSUPPORTED, "sig2 kernel is the certified-precision path"); }
-  static int32_t no_horizon() {
-    return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no fixed-horizon mode (horizon must be 0)");
-  }
-  static int32_t no_hard_log() {
-    return fail(PG_ERR_UNSUPPORTED, "sig2 kernel: no hard-case log (hard_log must be NULL)");
-  }
-  static int32_t decide_bad_activation(int activation) {
-    return fail(PG_ERR_UNSUPPORTED, "pg_sig2_decide: activation=%d, the sig2 kernel decides sigmoid networks only",
-                activation);
-  }
-  static int32_t decide_bad_shape() {
-    return fail(PG_ERR_UNSUPPORTED, "pg_sig2_decide: the sig2 kernel's shapes [6, 2..64, 2..64, 2..4] only");
-  }
-  static int32_t decide_no_bias() {
-    return fail(PG_ERR_UNSUPPORTED, "pg_sig2_decide: the sig2 kernel needs a network with bias");
-  }
-  static void game(int LN, int O, bool f64, bool advance, bool solo, int grid, hipStream_t s, const EvalParams &p) {
+struct Sig2Family : Hidden2Family {
+  static constexpr int kKernel = PG_KERNEL_SIG2, kActivation = PG_ACT_SIGMOID;
+  static constexpr const char *kName = "sig2";
+  static constexpr const char *kBadActivation =
+      "activation relu: the sig2 kernel evaluates sigmoid networks only (use RELU2)";
+  static constexpr const char *kBadShape = "sig2 kernel needs NETWORK_SHAPE [6, 2..64, 2..64, 2..4]";
+  static constexpr const char *kNoBias = "sig2 kernel needs a network with bias";
+  static constexpr const char *kNoHorizon = "sig2 kernel: no fixed-horizon mode (horizon must be 0)";
+  static constexpr const char *kNoHardLog = "sig2 kernel: no hard-case log (hard_log must be NULL)";
+  static constexpr const char *kDecideBadActivation =
+      "pg_sig2_decide: activation=%d, the sig2 kernel decides sigmoid networks only";
+  static constexpr const char *kDecideBadShape = "pg_sig2_decide: the sig2 kernel's shapes [6, 2..64, 2..64, 2..4] only";
+  static constexpr const char *kDecideNoBias = "pg_sig2_decide: the sig2 kernel needs a network with bias";
+  static void game(const EvalParams &p, bool f64, bool advance, bool solo, int grid, hipStream_t s) {
+    const int LN = lanes(p.nodes), O = p.nodes[3];
     if (solo) sig2_solo_game(LN, O, f64, advance, grid, s, p);
     else if (advance) PG_HIDDEN2_DISPATCH(k_sig2_adv, LN, O, f64, grid, s, p);
     else PG_HIDDEN2_DISPATCH(k_sig2, LN, O, f64, grid, s, p);
   }
-  static void decide(int LN, int O, bool f64, int grid, hipStream_t s, const CertDecideParams &p) {
-    PG_HIDDEN2_DISPATCH(k_sig2_decide, LN, O, f64, grid, s, p);
+  static void decide(const int32_t *nodes, bool f64, int grid, hipStream_t s, const DecideParams &p) {
+    PG_HIDDEN2_DISPATCH(k_sig2_decide, lanes(nodes), nodes[3], f64, grid, s, p);
   }
 };
 
-int32_t sig2_scope(const pg_eval_args &a) { return hidden2_scope<Sig2Family>(a); }
-
-int32_t launch_sig2(const EvalParams &p, int dtype, bool advance, bool solo, hipStream_t s) {
-  return hidden2_launch<Sig2Family>(p, dtype, advance, solo, s);
-}
+FamilyDesc sig2_family() { return family_desc<Sig2Family>(); }
 
 }  // namespace pg
 
 extern "C" int32_t pg_sig2_decide(const pg_relu_decide_args *a, void *stream) {
-  return pg::hidden2_decide<pg::Sig2Family>(a, stream);
+  return pg::family_decide<pg::Sig2Family>(a, stream);
 }
 #endif  // PG_SOLO_UNIT

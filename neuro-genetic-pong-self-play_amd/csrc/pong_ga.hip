@@ -19,12 +19,8 @@
 //                         arithmetic with activations staged in LDS (sigmoid or
 //                         ReLU; pg_general.hip).
 //   k_wide<NG,WT,ACT>     [6, H1<=512, H2<=512, O] networks, weights streamed (pg_wide.hip).
-//   k_relu<LN,U,O,WT>     [6, H<=256, O] ReLU networks (pg_relu.hip, pg_relu.hpp).
-//   k_relu2<LN,U1,U2,O,WT>  [6, H1<=64, H2<=64, O] ReLU networks (pg_relu2.hip, pg_hidden2.hpp).
-//   k_sig2<LN,U1,U2,O,WT>   [6, H1<=64, H2<=64, O] sigmoid networks (pg_sig2.hip, pg_hidden2.hpp).
-//                         These three share one game loop (pg_certgame.hpp).
-//   k_relu2_block<O,WT>   [6, H1<=128, H2<=128, O] ReLU networks, a block per game (pg_relu2_block.hip).
-//   k_sig2_block<O,WT>    [6, H1<=128, H2<=128, O] sigmoid networks, a block per game (pg_sig2_block.hip).
+//   the certified f32 families' kernels: one unit each, reached through the
+//                         family table below (family_of; pg_eval.hpp lists the units).
 //   k_fitness             sum(all_rewards) / GAMES_TO_PLAY in the reference order.
 //   k_forward_resident, k_physics_*   pg_forward's certified path and the SoA
 //                         Pong stepper (pg_physics_*): here because k_service's
@@ -373,12 +369,23 @@ static size_t split_records_bytes(const pg_eval_args *a) {
   return align256(service_records_bytes(a->n_genomes, a->opponents ? a->n_opponents : 0, L, U, a->net.nodes[2]));
 }
 
+// The certified f32 families (pg_eval.hpp's FamilyDesc): the one list of them here.  A new family is a
+// row; whether it takes the modifier bits, when its scope is asked and how it is launched are its own.
+// family_of(kernel): kernel's family, or NULL for a pg_kernel that is no certified f32 family's.
+static const FamilyDesc *family_of(int kernel) {
+  static const FamilyDesc kFamilies[] = {relu_family(),       relu2_family(), sig2_family(), relu2_block_family(),
+                                         sig2_block_family(), relu3_family(), sig3_family()};
+  for (const FamilyDesc &f : kFamilies)
+    if (f.kernel == kernel) return &f;
+  return nullptr;
+}
+
 // the modifier bits that take effect on kernel (resolve_kernel's) for a launch in its scope:
-// the closed-form advance on the certified f32 families' untraced launches, solo games on theirs and
+// the closed-form advance on the untraced launches of the families that take it, solo games on theirs and
 // on SPLIT's in split_solo_scope (the bit reaches SPLIT through PG_KERNEL_AUTO only: check_modifier_bits)
 static int modifiers_in_effect(int kernel, const pg_eval_args &a, bool advance, bool solo) {
-  const bool cert = kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2 ||
-                    kernel == PG_KERNEL_RELU3 || kernel == PG_KERNEL_SIG3;
+  const FamilyDesc *f = family_of(kernel);
+  const bool cert = f && f->modifiers;
   int bits = 0;
   if (advance && cert && !a.trace) bits |= PG_KERNEL_ADVANCE;
   if (solo && (cert || (kernel == PG_KERNEL_SPLIT && split_solo_scope(a)))) bits |= PG_KERNEL_SOLO;
@@ -431,12 +438,13 @@ static int32_t check_eval_ranges(const pg_eval_args *a) {
   return PG_OK;
 }
 
-// PG_KERNEL_ADVANCE and PG_KERNEL_SOLO go with the certified families' kernels, named or through AUTO
+// PG_KERNEL_ADVANCE and PG_KERNEL_SOLO go with the kernels of the families that have such instances
+// (FamilyDesc::modifiers), named or through AUTO.  The refusals below name the families of the day they
+// were worded; their text is pinned (tests/golden/), the table is what decides.
 // (SPLIT takes the solo bit through AUTO only: the refusal of an explicit SPLIT | SOLO is kept for now)
 static bool takes_modifier_bits(int kernel) {
-  return kernel == PG_KERNEL_AUTO || kernel == PG_KERNEL_RELU || kernel == PG_KERNEL_RELU2 || kernel == PG_KERNEL_SIG2 ||
-         kernel == PG_KERNEL_RELU3 || kernel == PG_KERNEL_SIG3;  // (RELU3 and SIG3 joined after the refusals' messages
-                                                                 // below were recorded)
+  const FamilyDesc *f = family_of(kernel);
+  return kernel == PG_KERNEL_AUTO || (f && f->modifiers);
 }
 
 static int32_t check_modifier_bits(int kernel, bool advance, bool solo) {
@@ -453,19 +461,15 @@ static int32_t check_modifier_bits(int kernel, bool advance, bool solo) {
 
 // Scope (pg_eval.hpp: each family states its own, activation first).  When a
 // kernel is asked is today's order of refusals, an asymmetry that is kept:
-// RELU2, RELU_WIDE, SIG2, RELU2_BLOCK, SIG2_BLOCK, RELU3 and SIG3 are refused out of scope on entry, even
-// for an empty launch (scope_on_entry); RELU, SPLIT and WIDE only after the
+// RELU_WIDE and every certified f32 family but RELU are refused out of scope
+// on entry, even for an empty launch (scope_on_entry, FamilyDesc's flag of
+// that name); RELU, SPLIT and WIDE only after the
 // n_genomes == 0 return -- for a network of the other activation before the
 // workspace check (scope_of_activation), for the rest at the launch (launch_games).
 static int32_t scope_on_entry(const pg_eval_args &a) {
-  if (a.kernel == PG_KERNEL_RELU2) return relu2_scope(a);
   if (a.kernel == PG_KERNEL_RELU_WIDE) return wide_scope(a, true);
-  if (a.kernel == PG_KERNEL_SIG2) return sig2_scope(a);
-  if (a.kernel == PG_KERNEL_RELU2_BLOCK) return relu2_block_scope(a);
-  if (a.kernel == PG_KERNEL_SIG2_BLOCK) return sig2_block_scope(a);
-  if (a.kernel == PG_KERNEL_RELU3) return relu3_scope(a);
-  if (a.kernel == PG_KERNEL_SIG3) return sig3_scope(a);
-  return PG_OK;
+  const FamilyDesc *f = family_of(a.kernel);
+  return f && f->scope_on_entry ? f->scope(a) : PG_OK;
 }
 
 // the buffers and modes of a launch that plays games (n_genomes > 0)
@@ -488,17 +492,19 @@ static int32_t check_eval_buffers(const pg_eval_args *a) {
   return PG_OK;
 }
 
-// ReLU networks run on k_relu, k_relu2, k_wide's ReLU instances or k_general:
-// whole episodes, no hard-case log.  The fixed horizon is the SPLIT kernel's.
+// ReLU networks run on the ReLU families' kernels, k_wide's ReLU instances or
+// k_general: whole episodes, no hard-case log.  The fixed horizon is the SPLIT kernel's.
 static int32_t scope_of_activation(const pg_eval_args &a) {
+  const FamilyDesc *f = family_of(a.kernel);
   if (a.net.activation == PG_ACT_RELU) {
     // (a sigmoid-only kernel's scope of a ReLU network is its refusal of the activation)
     if (a.kernel == PG_KERNEL_SPLIT) return split_scope(a);
     if (a.kernel == PG_KERNEL_WIDE) return wide_scope(a, false);
     if (a.horizon > 0) return fail(PG_ERR_UNSUPPORTED, "activation relu: no fixed-horizon mode (horizon must be 0)");
     if (a.hard_log) return fail(PG_ERR_UNSUPPORTED, "activation relu: no hard-case log (hard_log must be NULL)");
-  } else if (a.kernel == PG_KERNEL_RELU) {  // (the same of a sigmoid network)
-    return relu_scope(a);
+  } else if (f && !f->scope_on_entry) {  // (the same of a sigmoid network on a family scoped at the launch: RELU)
+    const int32_t rc = f->scope(a);
+    if (rc != PG_OK) return rc;
   }
   if (a.horizon > 0 && a.trace) return fail(PG_ERR_INVALID, "horizon mode runs untraced (trace must be NULL)");
   if (a.horizon > 0 && resolve_kernel(&a) != PG_KERNEL_SPLIT)
@@ -544,13 +550,17 @@ static EvalParams eval_params(const pg_eval_args *a) {
   return p;
 }
 
-// the games on kernel (resolve_kernel's); RELU_WIDE, RELU2, SIG2, RELU2_BLOCK and SIG2_BLOCK were found in scope
-// on entry
+// the games on kernel (resolve_kernel's); RELU_WIDE and the families with scope_on_entry were found in scope
+// on entry, the others are asked here
 // (advance, solo: modifiers_in_effect's)
 static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bool advance, bool solo, hipStream_t s) {
   void *const after_base = (char *)a->workspace + eval_base_workspace(a);
   const int dtype = a->net.dtype;
   int32_t rc = PG_OK;
+  if (const FamilyDesc *f = family_of(kernel)) {
+    if (!f->scope_on_entry) rc = f->scope(*a);
+    return rc != PG_OK ? rc : f->launch(p, dtype, advance, solo, s);
+  }
   switch (kernel) {
     case PG_KERNEL_RELU_WIDE:
       return launch_wide(p, dtype, after_base, s);
@@ -570,21 +580,6 @@ static int32_t launch_games(int kernel, const pg_eval_args *a, EvalParams &p, bo
       // retired layouts (correct, measured slower than SPLIT; removed in round 4)
       return fail(PG_ERR_UNSUPPORTED, "the %s kernel was retired (DESIGN 4.1b-c); use SPLIT",
                   kernel == PG_KERNEL_RESIDENT ? "resident" : "staged");
-    case PG_KERNEL_RELU:
-      rc = relu_scope(*a);
-      return rc != PG_OK ? rc : launch_relu(p, dtype, advance, solo, s);
-    case PG_KERNEL_RELU2:
-      return launch_relu2(p, dtype, advance, solo, s);
-    case PG_KERNEL_SIG2:
-      return launch_sig2(p, dtype, advance, solo, s);
-    case PG_KERNEL_RELU2_BLOCK:
-      return launch_relu2_block(p, dtype, s);
-    case PG_KERNEL_SIG2_BLOCK:
-      return launch_sig2_block(p, dtype, s);
-    case PG_KERNEL_RELU3:
-      return launch_relu3(p, dtype, advance, solo, s);
-    case PG_KERNEL_SIG3:
-      return launch_sig3(p, dtype, advance, solo, s);
     case PG_KERNEL_GENERAL:
       return launch_general(p, dtype, s);
     default:
